@@ -13,7 +13,18 @@ collective: weak scaling). value = audio-seconds of all ranks / max-rank time.
 ranks itself (a child `torch.distributed.run`, before anything touches the GPU)
 and exits with its status; under a launcher WORLD_SIZE must equal --gpus.
 
-Extra keys of the line (none of them is `value`):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up
+steps and the clock settle, the N timed steps, the outputs of the last timed step if `--dump-outputs DIR` is
+given, and the result line (value, ms_per_step, K1's events of the timed region). Everything below -- the
+checks against the oracle, the CPU baselines, the per-kernel breakdown and roofline, and the other workloads
+-- runs only with `--full`; the `--no-*` and per-leg options select among the legs of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left in the engine, as a caller reads it back
+(aid_result_counts, aid_result_hashes), to DIR/<name>.npy in float64 (every value is an integer below 2^32, so
+exact): `counts` [clips], and `hash` / `t1` [sum of counts], the records' two 32-bit halves, clips concatenated
+in order. The inputs are generated from fixed seeds, so two runs with the same arguments dump the same data.
+
+Extra keys of the `--full` line (none of them is `value`):
   * roofline -- the dominant kernel's algorithmic HBM bytes per launch / its mean launch
     time from HIP events on the launch stream in the timed region, against 8.0 TB/s; plus
     which unit binds: traffic_frac (PMC bytes) and valu_issue_frac (SQ_INSTS_VALU) per
@@ -354,6 +365,66 @@ def roofline_units(kern: dict, pmc: dict, sq: dict) -> dict:
             d["lds_insts"] = c["SQ_INSTS_LDS"]
         out[k] = d
     return out
+
+
+def dump_outputs(eng, out_dir: Path, rank: int = 0) -> dict:
+    """The last extraction's results as a caller of aid_extract receives them (counts per clip; every clip's
+    records hash | t1 << 32, split into their 32-bit halves), as float64 .npy files under `out_dir`. Ranks
+    above 0 (N > 1) write <name>_rank<r>.npy. Returns {name: elements}."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    counts = eng.counts()
+    recs = [eng.hashes(c) for c in range(len(counts))]
+    rec = np.concatenate(recs) if recs else np.zeros(0, np.uint64)
+    arrays = {"counts": counts.astype(np.float64),
+              "hash": (rec & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "t1": (rec >> np.uint64(32)).astype(np.float64)}
+    sfx = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}{sfx}.npy", a)
+    return {k: int(a.size) for k, a in arrays.items()}
+
+
+def headline_roofline(kern: dict, frames: int, samples: int, step_s: float) -> dict:
+    """The `roofline` object of the line: the dominant extraction kernel's algorithmic bytes over its time,
+    the committed counters per kernel, and the whole step (step_s seconds) on the same accounting."""
+    alg = algorithmic_bytes(frames, samples)
+    dom = max(("stft_power", "peak_pick"), key=lambda k: kern[k]["ms_per_launch"] if k in kern else 0.0)
+    dom_ms = kern[dom]["ms_per_launch"]
+    achieved = alg[dom] / (dom_ms * 1e-3) / 1e9
+    pmc, pmc_src = load_pmc()
+    sq, sq_src = load_sq()
+    units = roofline_units(kern, pmc, sq)
+    return {
+        "kernel": dom,
+        "bound": "hbm",
+        "achieved": round(achieved, 1),
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": pmc.get(dom),
+        "algorithmic_bytes_per_launch": alg[dom],
+        "duration_ms": round(dom_ms, 5),
+        "duration_source": kern[dom]["pass"],
+        "traffic_frac": units.get(dom, {}).get("traffic_frac"),
+        "valu_issue_frac": units.get(dom, {}).get("valu_issue_frac"),
+        "per_kernel": units,
+        "traffic_source": pmc_src,
+        "sq_source": sq_src,
+        "extraction_kernels_ms_per_step": round(sum(v["ms_per_launch"] for v in kern.values()), 4),
+        # the whole step against the same staged-dataflow accounting (K1 + K2 bytes of SURVEY 8(d); K3's
+        # mask reads and record writes are < 1 % and left out): how far the pipeline is from streaming
+        "step_staged_bytes": alg["stft_power"] + alg["peak_pick"],
+        "step_achieved": round((alg["stft_power"] + alg["peak_pick"]) / step_s / 1e9, 1),
+        # the step on the bytes it actually moves: PMC bytes of K1 + K2 + K3 per step / ms_per_step / 8 TB/s
+        "step_traffic_bytes": (sum(pmc[k] for k in KERNEL_PMC) if all(k in pmc for k in KERNEL_PMC) else None),
+        "step_traffic_frac": (round(sum(pmc[k] for k in KERNEL_PMC) / step_s / 1e9 / HBM_PEAK_GBS, 4)
+                              if all(k in pmc for k in KERNEL_PMC) else None),
+        "note": "frac = SURVEY 8(d) staged-dataflow bytes (PCM + the full power plane) / the kernel's time. K1 "
+                "stores only hot 64-bin blocks and K2 reads only those, so the bytes actually moved (traffic, PMC "
+                "2 x FETCH_SIZE + WRITE_SIZE) are below that on band-limited audio: traffic_frac says how busy HBM "
+                "is, valu_issue_frac (SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x duration)) how busy the "
+                "vector issue is -- the larger of the two is the binding unit",
+    }
 
 
 def run_steps(eng, pcm_ptr, offs, stream, steps, torch):
@@ -1110,6 +1181,12 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the checks against the oracle, the CPU baselines, the per-kernel "
+                         "breakdown / roofline and the other workloads (fullband, catalog + exact lane, service, "
+                         "stream); without it only the headline is measured and the options below are not used")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="write the last timed step's results (counts, hash, t1) to DIR/<name>.npy as float64")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--settle", type=float, default=0.1,
                     help="seconds of untimed steps after the warmup steps (GPU clock ramp); 0 = none")
@@ -1238,8 +1315,13 @@ def main() -> int:
     elapsed = time.perf_counter() - t0
     prof = eng.profile_read(reset=True)
     eng.profile_enable(False)
-    kern = {k: {**v, "pass": "untimed breakdown"}
-            for k, v in breakdown(eng, pcm.data_ptr(), offs, stream, max(1, min(args.steps, 20)), torch).items()}
+    dumped = None
+    if args.dump_outputs is not None:  # the last timed step's results, before anything else runs on the engine
+        dumped = _agreed(lambda: dump_outputs(eng, args.dump_outputs, rank), "dump outputs", dist)
+    kern = {}
+    if args.full:  # an untimed pass of its own with events on every extraction kernel
+        kern = {k: {**v, "pass": "untimed breakdown"}
+                for k, v in breakdown(eng, pcm.data_ptr(), offs, stream, max(1, min(args.steps, 20)), torch).items()}
     for k, (ms, cnt) in prof.items():  # the timed region's own events win where they exist
         if cnt:
             kern[k] = {"ms_per_launch": ms / cnt, "launches": cnt, "pass": "timed region"}
@@ -1247,46 +1329,57 @@ def main() -> int:
 
     audio_s = world * CLIPS * CLIP_S * args.steps
     value = audio_s / elapsed
-    alg = algorithmic_bytes(frames, CLIPS * n)
-    dom = max(("stft_power", "peak_pick"), key=lambda k: kern[k]["ms_per_launch"] if k in kern else 0.0)
-    dom_ms = kern[dom]["ms_per_launch"]
-    achieved = alg[dom] / (dom_ms * 1e-3) / 1e9
-    pmc, pmc_src = load_pmc()
-    sq, sq_src = load_sq()
-    units = roofline_units(kern, pmc, sq)
-    roofline = {
-        "kernel": dom,
-        "bound": "hbm",
-        "achieved": round(achieved, 1),
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4),
-        "traffic": pmc.get(dom),
-        "algorithmic_bytes_per_launch": alg[dom],
-        "duration_ms": round(dom_ms, 5),
-        "duration_source": kern[dom]["pass"],
-        "traffic_frac": units.get(dom, {}).get("traffic_frac"),
-        "valu_issue_frac": units.get(dom, {}).get("valu_issue_frac"),
-        "per_kernel": units,
-        "traffic_source": pmc_src,
-        "sq_source": sq_src,
-        "extraction_kernels_ms_per_step": round(sum(v["ms_per_launch"] for v in kern.values()), 4),
-        # the whole step against the same staged-dataflow accounting (K1 + K2 bytes of SURVEY 8(d); K3's
-        # mask reads and record writes are < 1 % and left out): how far the pipeline is from streaming
-        "step_staged_bytes": alg["stft_power"] + alg["peak_pick"],
-        "step_achieved": round((alg["stft_power"] + alg["peak_pick"]) / (elapsed / args.steps) / 1e9, 1),
-        # the step on the bytes it actually moves: PMC bytes of K1 + K2 + K3 per step / ms_per_step / 8 TB/s
-        "step_traffic_bytes": (sum(pmc[k] for k in KERNEL_PMC) if all(k in pmc for k in KERNEL_PMC) else None),
-        "step_traffic_frac": (round(sum(pmc[k] for k in KERNEL_PMC) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
-                              if all(k in pmc for k in KERNEL_PMC) else None),
-        "note": "frac = SURVEY 8(d) staged-dataflow bytes (PCM + the full power plane) / the kernel's time. K1 "
-                "stores only hot 64-bin blocks and K2 reads only those, so the bytes actually moved (traffic, PMC "
-                "2 x FETCH_SIZE + WRITE_SIZE) are below that on band-limited audio: traffic_frac says how busy HBM "
-                "is, valu_issue_frac (SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x duration)) how busy the "
-                "vector issue is -- the larger of the two is the binding unit",
-    }
+    roofline = fullband = cpu = par = None  # --full only
 
-    cpu = par = None
+    def make_line(catalog, service, stream) -> dict:
+        return {
+            "metric": METRIC,
+            "value": round(value, 1),
+            "unit": "audio-s/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_steps": settle_steps,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (aid_synth: seed-42 integer-exact partials + noise, generated in HBM)",
+            "config": {
+                "workload": "BASELINE configs[1]: 256 x 10 s 44.1 kHz mono clips, fingerprint extraction per GPU",
+                "clips_per_gpu": CLIPS,
+                "clip_seconds": CLIP_S,
+                "sample_rate": SR,
+                "n_fft": 2048,
+                "hop": 512,
+                "parallelism": f"clip-sharded x{world} (no data-path collective)",
+                "process_group": dist.get_backend() if dist else None,
+            },
+            "realtime_factor_per_gpu": round(value / world, 1),
+            "hashes_per_step_per_gpu": hashes_per_step,
+            "kernels": kern,
+            "roofline": roofline,
+            "fullband": fullband,
+            "catalog": catalog,
+            "service": service,
+            "stream": stream,
+            "cpu_baseline": cpu,
+            "parity": par,
+            "full": bool(args.full),
+            "dump_outputs": dumped,
+        }
+
+    if not args.full:  # a plain run: the headline and nothing else
+        del pcm
+        eng.close()
+        if rank == 0:
+            print(json.dumps(make_line(None, None, None)), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return 0
+
+    roofline = headline_roofline(kern, frames, CLIPS * n, elapsed / args.steps)
     host = None
     if rank == 0:
         host = pcm.view(CLIPS, n).cpu().numpy()
@@ -1362,43 +1455,6 @@ def main() -> int:
         if not lp:
             return True
         return bool(lp.get("records_bit_exact") and lp.get("rows_bit_exact") and lp.get("lane_equal"))
-
-    def make_line(catalog, service, stream) -> dict:
-        return {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "audio-s/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_steps": settle_steps,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (aid_synth: seed-42 integer-exact partials + noise, generated in HBM)",
-            "config": {
-                "workload": "BASELINE configs[1]: 256 x 10 s 44.1 kHz mono clips, fingerprint extraction per GPU",
-                "clips_per_gpu": CLIPS,
-                "clip_seconds": CLIP_S,
-                "sample_rate": SR,
-                "n_fft": 2048,
-                "hop": 512,
-                "parallelism": f"clip-sharded x{world} (no data-path collective)",
-                "process_group": dist.get_backend() if dist else None,
-            },
-            "realtime_factor_per_gpu": round(value / world, 1),
-            "hashes_per_step_per_gpu": hashes_per_step,
-            "kernels": kern,
-            "roofline": roofline,
-            "fullband": fullband,
-            "catalog": catalog,
-            "service": service,
-            "stream": stream,
-            "cpu_baseline": cpu,
-            "parity": par,
-        }
 
     if args.leg_deadline > 0 and not (args.no_catalog and args.no_service and args.no_stream):
         threading.Thread(target=watchdog, daemon=True).start()

@@ -45,19 +45,19 @@ for step in "$@"; do
     mtests) timeout -k 10 600 python -u -m pytest tests/test_gpu_match.py tests/test_gpu_match_load.py tests/test_gpu_lane_parity.py tests/test_gpu_exact.py -m gpu -x -v --timeout 120 --timeout-method thread > $O/gpu_mtests.txt 2>&1 ;;
     xtests) timeout -k 10 400 python -u -m pytest tests/test_gpu_extract.py -m gpu -x -v --timeout 120 --timeout-method thread > $O/gpu_xtests.txt 2>&1 ;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 ;;
-    bench) timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err ;;
+    bench) timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err ;;
     music) timeout -k 10 900 python3 -u probes/music_eval.py --tracks 1000 --queries 500 --negatives 100 --workers 16 > $O/music.json 2> $O/music.err ;;
-    prof) timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --no-catalog --no-stream --no-service > $O/prof_bench.json 2> $O/prof.err ;;
+    prof) timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full --no-catalog --no-stream --no-service > $O/prof_bench.json 2> $O/prof.err ;;
     pmc) bash profiles/run_rocprof.sh $TAG > $O/pmc_prof.log 2>&1 && bash profiles/run_sq.sh $TAG > $O/pmc_sq.log 2>&1 ;;
     k5)
-      B="python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-service --no-stream"
+      B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-service --no-stream"
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $O/k5/trace -o run --output-format csv -- $B > $O/k5_trace.json 2> $O/k5_trace.err &&
       timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T -d $O/k5/fetch -o run --output-format csv -- $B > $O/k5_fetch.json 2> $O/k5_fetch.err &&
       timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -T -d $O/k5/write -o run --output-format csv -- $B > $O/k5_write.json 2> $O/k5_write.err ;;
     k5req)
-      B="python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-service --no-stream"
+      B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-service --no-stream"
       timeout -k 10 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCP_TCC_READ_REQ_sum -T -d $O/k5/req -o run --output-format csv -- $B > $O/k5_req.json 2> $O/k5_req.err ;;
-    segv) timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/segv.json 2> $O/segv.err ;;
+    segv) timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/segv.json 2> $O/segv.err ;;
     counters) timeout -k 10 60 rocprofv3 -L > $O/counters.txt 2>&1 ;;
     k2ab) timeout -k 10 900 bash probes/run_ab_lib.sh $O/k2_ab.txt ${K2AB_VARIANT:?set K2AB_VARIANT} 3 > $O/k2ab.log 2>&1 ;;
     streamprof) timeout -k 10 300 python3 probes/stream_host_profile.py > $O/stream_prof.txt 2> $O/stream_prof.err ;;
@@ -70,11 +70,11 @@ for step in "$@"; do
     svcab)
       rc=0
       for r in 1 2; do for v in "0 0" "1 0" "1 16" "1 32"; do set -- $v
-        timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-pipeline $1 --service-split-min $2 > $O/svc_p$1_s$2_r$r.json 2> $O/svc_p$1_s$2_r$r.err || { rc=$?; break 2; }
+        timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-pipeline $1 --service-split-min $2 > $O/svc_p$1_s$2_r$r.json 2> $O/svc_p$1_s$2_r$r.err || { rc=$?; break 2; }
       done; done
       [ $rc -eq 0 ] ;;
     k2mall) timeout -k 10 400 python3 probes/k2_mall_probe.py 3 > $O/k2_mall.json 2> $O/k2_mall.err ;;
-    gloo4) AIDFP_BENCH_BACKEND=gloo timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 4 --steps 5 --warmup 2 --no-cpu > $O/gloo4.json 2> $O/gloo4.err ;;
+    gloo4) AIDFP_BENCH_BACKEND=gloo timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 4 --steps 5 --warmup 2 --no-cpu > $O/gloo4.json 2> $O/gloo4.err ;;
     k6pmc)
       P="python3 probes/stream_host_profile.py --seconds 30"
       timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY -T -d $O/k6pmc/sq -o run --output-format csv -- $P > $O/k6pmc_sq.txt 2> $O/k6pmc_sq.err &&
@@ -92,7 +92,7 @@ for step in "$@"; do
       rc=0
       for r in 1 2 3; do for v in "20 0.1" "100 0.1" "100 0.5"; do set -- $v
         echo "== steps $1 settle $2 round $r" >> $O/settle_ab.txt
-        timeout -k 10 200 python3 bench.py --steps $1 --settle $2 --no-cpu --no-fullband --no-catalog --no-service --no-stream > $O/settle_tmp.json 2>/dev/null || { rc=$?; break 2; }
+        timeout -k 10 200 python3 bench.py --full --steps $1 --settle $2 --no-cpu --no-fullband --no-catalog --no-service --no-stream > $O/settle_tmp.json 2>/dev/null || { rc=$?; break 2; }
         tail -1 $O/settle_tmp.json | cut -c1-220 >> $O/settle_ab.txt
       done; done
       [ $rc -eq 0 ] ;;
@@ -108,29 +108,29 @@ for step in "$@"; do
     copyab)
       rc=0
       for r in 1 2 3; do for m in 4194304 2097152; do
-        AIDFP_COPY_MIN_FLOATS=$m timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc_copy${m}_r$r.json 2> $O/svc_copy${m}_r$r.err || { rc=$?; break 2; }
+        AIDFP_COPY_MIN_FLOATS=$m timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc_copy${m}_r$r.json 2> $O/svc_copy${m}_r$r.err || { rc=$?; break 2; }
       done; done
       [ $rc -eq 0 ] ;;
     copythr)
       rc=0
       for r in 1 2 3; do for t in 4 8; do
-        AIDFP_COPY_THREADS=$t timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc_thr${t}_r$r.json 2> $O/svc_thr${t}_r$r.err || { rc=$?; break 2; }
+        AIDFP_COPY_THREADS=$t timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc_thr${t}_r$r.json 2> $O/svc_thr${t}_r$r.err || { rc=$?; break 2; }
       done; done
       [ $rc -eq 0 ] ;;
     winab)
       rc=0
       for r in 1 2 3; do for w in ${WINAB_MS:-0.5 0.2 1.0}; do
-        timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-window-ms $w > $O/svc_win${w}_r$r.json 2> $O/svc_win${w}_r$r.err || { rc=$?; break 2; }
+        timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-window-ms $w > $O/svc_win${w}_r$r.json 2> $O/svc_win${w}_r$r.err || { rc=$?; break 2; }
       done; done
       [ $rc -eq 0 ] ;;
     splitab)
       rc=0
       for r in 1 2 3; do for m in ${SPLITAB_MIN:-16 8 32}; do
-        timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-split-min $m > $O/svc_split${m}_r$r.json 2> $O/svc_split${m}_r$r.err || { rc=$?; break 2; }
+        timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream --service-split-min $m > $O/svc_split${m}_r$r.json 2> $O/svc_split${m}_r$r.err || { rc=$?; break 2; }
       done; done
       [ $rc -eq 0 ] ;;
     svc)
-      timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc.json 2> $O/svc.err ;;
+      timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-fullband --no-catalog --no-stream > $O/svc.json 2> $O/svc.err ;;
     k6ab)
       rc=0
       for r in 1 2 3; do for lib in product ${K6AB_VARIANTS:?set K6AB_VARIANTS}; do

@@ -13,5 +13,5 @@ sys.path.insert(0, str(ROOT / "audio-ident_amd"))
 import aidfp.engine as E  # noqa: E402
 
 E._COPY_MIN = int(sys.argv[1])
-sys.argv = [str(ROOT / "bench.py"), "--no-cpu", "--no-fullband", "--no-catalog", "--no-stream"]
+sys.argv = [str(ROOT / "bench.py"), "--full", "--no-cpu", "--no-fullband", "--no-catalog", "--no-stream"]
 runpy.run_path(str(ROOT / "bench.py"), run_name="__main__")

@@ -61,6 +61,36 @@ def test_cpu_baseline_names_the_host_and_numpy_leg():
     assert cpu["numpy_scipy"]["value_1proc"] > 0 and cpu["numpy_scipy"]["value_pool"] > 0
 
 
+def test_dump_outputs_writes_the_records_exactly(tmp_path):
+    """--dump-outputs: counts and the records' 32-bit halves as float64 .npy, clips in order, nothing lost."""
+
+    class _Eng(_Records):
+        def counts(self):
+            return np.array([len(r) for r in self.recs], dtype=np.int64)
+
+    recs = [np.array([0xFFFFFFFF_FFFFFFFF, 0x00000001_80000000, 7], dtype=np.uint64), np.zeros(0, np.uint64),
+            np.array([0x12345678_9ABCDEF0], dtype=np.uint64)]
+    sizes = bench.dump_outputs(_Eng(recs), tmp_path / "out")
+    assert sizes == {"counts": 3, "hash": 4, "t1": 4}
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in sizes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["counts"].tolist() == [3, 0, 1]
+    back = got["hash"].astype(np.uint64) | (got["t1"].astype(np.uint64) << np.uint64(32))
+    assert np.array_equal(back, np.concatenate(recs))
+    assert bench.dump_outputs(_Eng(recs), tmp_path / "out", rank=2) == sizes
+    assert (tmp_path / "out" / "hash_rank2.npy").exists()
+
+
+def test_cli_offers_full_and_dump_outputs():
+    """The two options the plain / full split rests on are there."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, str(bench.ROOT / "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_launch_plan():
     assert bench.launch_plan(1, {}) == "run"
     assert bench.launch_plan(2, {}) == "spawn"
