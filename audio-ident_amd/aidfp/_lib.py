@@ -149,6 +149,11 @@ SIGNATURES = [
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),
 ]
+# the _s16 twins (integer PCM, FPSPEC 8): the sibling's signature, int16 samples behind the PCM pointer
+SIGNATURES += [(name + "_s16", res, args) for name, res, args in SIGNATURES
+               if name in ("aid_extract", "aid_query_pcm", "aid_query_pcm_submit", "aid_query_windows",
+                           "aid_query_windows_submit", "aid_exact_lane", "aid_resample", "aid_resample_batch_split")]
+PCM_FORMATS = ("f32", "s16")
 
 _lib = None
 

@@ -167,14 +167,35 @@ def _new_slot() -> _PinnedSlot:
     return sl
 
 
-def _host_concat(arrs: list[np.ndarray], total: int, slot: "_PinnedSlot | None" = None) -> np.ndarray:
+def _fmt_suffix(fmt: str) -> str:
+    """The C entry points' suffix of a PCM format name: none for "f32", "_s16" for "s16"."""
+    if fmt not in L.PCM_FORMATS:
+        raise ValueError(f"unknown PCM format {fmt!r} (one of {', '.join(L.PCM_FORMATS)})")
+    return "" if fmt == "f32" else "_s16"
+
+
+def _host_clips(clips: Sequence[np.ndarray], fmt: str) -> list[np.ndarray]:
+    """The clips as flat contiguous arrays of the format's dtype. "f32" casts whatever it is given, as ever; "s16"
+    takes int16 arrays only: no dispatch on dtype, and no silent narrowing of float samples."""
+    if _fmt_suffix(fmt) == "":
+        return [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
+    arrs = [np.asarray(c) for c in clips]
+    for a in arrs:
+        if a.dtype != np.int16:
+            raise ValueError(f'fmt="s16" takes int16 clips, got {a.dtype}')
+    return [np.ascontiguousarray(a).ravel() for a in arrs]
+
+
+def _host_concat(arrs: list[np.ndarray], total: int, slot: "_PinnedSlot | None" = None,
+                 dtype=np.float32) -> np.ndarray:
     """The clips concatenated into one host array for AID_PCM_HOST. Up to _PINNED_MAX samples it is a page-locked
     buffer (grown on demand), so the engine's single H2D copy of the span runs as a DMA instead of through the
     runtime's pageable staging (coalesced service queries). By default the calling thread's buffer: the engine call
     has finished with it when it returns (every synchronous host-PCM entry point syncs before returning its results);
-    a submitted query passes its own `slot`, held until it is collected."""
+    a submitted query passes its own `slot`, held until it is collected. dtype int16 (integer PCM): the same
+    page-locked bytes viewed as int16, so a slot serves either format."""
     if total == 0:
-        return np.zeros(1, dtype=np.float32)
+        return np.zeros(1, dtype=dtype)
     if total <= _PINNED_MAX:
         try:
             import torch
@@ -185,11 +206,12 @@ def _host_concat(arrs: list[np.ndarray], total: int, slot: "_PinnedSlot | None" 
                 if sl is None:
                     sl = _pinned.slot = _new_slot()
             buf = sl.buf
-            if buf is None or buf.numel() < total:
+            need = total if dtype == np.float32 else (total + 1) // 2  # floats of page-locked memory
+            if buf is None or buf.numel() < need:
                 if _finalizing():
                     raise RuntimeError("interpreter shutting down")
-                buf = sl.buf = torch.empty(max(total, 1 << 20), dtype=torch.float32, pin_memory=True)
-            out = buf.numpy()[:total]
+                buf = sl.buf = torch.empty(max(need, 1 << 20), dtype=torch.float32, pin_memory=True)
+            out = buf.numpy().view(dtype)[:total]
             _concat_into(arrs, out)
             return out
         except (ImportError, RuntimeError):  # no torch / no device: pageable memory works the same, slower
@@ -272,22 +294,28 @@ class Engine:
         return int(self._lib.aid_hash_capacity(self._h, int(n)))
 
     # -- extraction --
-    def extract_host(self, clips: Sequence[np.ndarray]) -> list[np.ndarray]:
-        """Fingerprint host clips; returns one uint64 record array (hash | t1 << 32) per clip."""
-        arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
+    def _fn(self, name: str, fmt: str):
+        """The C entry point `name` of a PCM format ("f32": itself, "s16": its _s16 twin)."""
+        return getattr(self._lib, name + _fmt_suffix(fmt))
+
+    def extract_host(self, clips: Sequence[np.ndarray], fmt: str = "f32") -> list[np.ndarray]:
+        """Fingerprint host clips; returns one uint64 record array (hash | t1 << 32) per clip. fmt="s16": the clips
+        are int16 PCM (x = q / 32768), staged and read as such."""
+        arrs = _host_clips(clips, fmt)
         offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
         if arrs:
             offsets[1:] = np.cumsum([len(a) for a in arrs])
-        pcm = _host_concat(arrs, int(offsets[-1]))
-        check(self._lib.aid_extract(self._h, _p(pcm), _p(offsets), len(arrs), AID_PCM_HOST, None))
+        pcm = _host_concat(arrs, int(offsets[-1]), dtype=arrs[0].dtype if arrs else np.float32)
+        check(self._fn("aid_extract", fmt)(self._h, _p(pcm), _p(offsets), len(arrs), AID_PCM_HOST, None))
         self.n_clips = len(arrs)
         return [self.hashes(c) for c in range(len(arrs))]
 
-    def extract_device(self, pcm_ptr: int, offsets: np.ndarray, stream: int | None = None) -> None:
-        """Asynchronous extraction of device PCM; offsets = host int64[n_clips+1] (odd offsets allowed)."""
+    def extract_device(self, pcm_ptr: int, offsets: np.ndarray, stream: int | None = None, fmt: str = "f32") -> None:
+        """Asynchronous extraction of device PCM; offsets = host int64[n_clips+1] (odd offsets allowed), in samples
+        of `fmt` (float32, or int16 with fmt="s16")."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        check(self._lib.aid_extract(self._h, ctypes.c_void_p(pcm_ptr), _p(offsets), len(offsets) - 1,
-                                    AID_PCM_DEVICE, ctypes.c_void_p(stream) if stream else None))
+        check(self._fn("aid_extract", fmt)(self._h, ctypes.c_void_p(pcm_ptr), _p(offsets), len(offsets) - 1,
+                                           AID_PCM_DEVICE, ctypes.c_void_p(stream) if stream else None))
         self.n_clips = len(offsets) - 1
 
     def sync(self) -> None:
@@ -410,12 +438,13 @@ class Engine:
         return int(self._lib.aid_resample_len(int(n), int(sr_in), int(sr_out)))
 
     def resample(self, src_ptr: int, n: int, channels: int, sr_in: int, sr_out: int, dst_ptr: int, cap: int,
-                 stream: int | None = None) -> int:
-        """Asynchronous: n frames of `channels` floats at sr_in -> mono at sr_out; returns the output length."""
+                 stream: int | None = None, fmt: str = "f32") -> int:
+        """Asynchronous: n frames of `channels` floats (int16 with fmt="s16") at sr_in -> mono float at sr_out;
+        returns the output length."""
         m = ctypes.c_int64(0)
-        check(self._lib.aid_resample(self._h, ctypes.c_void_p(src_ptr), int(n), int(channels), int(sr_in),
-                                     int(sr_out), ctypes.c_void_p(dst_ptr), int(cap), ctypes.byref(m),
-                                     ctypes.c_void_p(stream) if stream else None))
+        check(self._fn("aid_resample", fmt)(self._h, ctypes.c_void_p(src_ptr), int(n), int(channels), int(sr_in),
+                                            int(sr_out), ctypes.c_void_p(dst_ptr), int(cap), ctypes.byref(m),
+                                            ctypes.c_void_p(stream) if stream else None))
         return int(m.value)
 
     def resample_range(self, src_ptr: int, in_base: int, n: int, channels: int, sr_in: int, sr_out: int,
@@ -437,14 +466,17 @@ class Engine:
 
     def resample_batch_split(self, hist_ptr: int, hist_stride: int, hist_n: int, src_ptr: int, src_stride: int,
                              n_streams: int, in_base: int, n: int, channels: int, sr_in: int, sr_out: int, m_first: int,
-                             count: int, dst_ptr: int, dst_stride: int, stream: int | None = None) -> None:
+                             count: int, dst_ptr: int, dst_stride: int, stream: int | None = None,
+                             fmt: str = "f32") -> None:
         """resample_batch over stream frames [in_base - hist_n, in_base) at hist_ptr then [in_base, in_base + n) at
-        src_ptr (aid_resample_batch_split): a chunk is read in place, only its predecessor's tail is kept."""
-        check(self._lib.aid_resample_batch_split(self._h, ctypes.c_void_p(hist_ptr), int(hist_stride), int(hist_n),
-                                                 ctypes.c_void_p(src_ptr), int(src_stride), int(n_streams),
-                                                 int(in_base), int(n), int(channels), int(sr_in), int(sr_out),
-                                                 int(m_first), int(count), ctypes.c_void_p(dst_ptr), int(dst_stride),
-                                                 ctypes.c_void_p(stream) if stream else None))
+        src_ptr (aid_resample_batch_split): a chunk is read in place, only its predecessor's tail is kept.
+        fmt="s16": hist and src are int16 and their strides count int16 (hist_n = 0 / n_streams = 1 give the
+        batch and range forms)."""
+        check(self._fn("aid_resample_batch_split", fmt)(
+            self._h, ctypes.c_void_p(hist_ptr), int(hist_stride), int(hist_n), ctypes.c_void_p(src_ptr),
+            int(src_stride), int(n_streams), int(in_base), int(n), int(channels), int(sr_in), int(sr_out),
+            int(m_first), int(count), ctypes.c_void_p(dst_ptr), int(dst_stride),
+            ctypes.c_void_p(stream) if stream else None))
 
     def resample_plan(self, sr_in: int, sr_out: int):
         v = [ctypes.c_int32() for _ in range(4)]
@@ -577,28 +609,28 @@ class Engine:
         check(self._lib.aid_query_extracted(self._h, rows.ctypes.data, _p(nrows)))
         return self._rows(rows, nrows, nq)
 
-    def query_pcm(self, clips: Sequence[np.ndarray]) -> list[np.ndarray]:
+    def query_pcm(self, clips: Sequence[np.ndarray], fmt: str = "f32") -> list[np.ndarray]:
         """Extract + match host clips in one engine call (aid_query_pcm; thread-safe as a unit)."""
-        arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
+        arrs = _host_clips(clips, fmt)
         nq = len(arrs)
         if nq == 0:
             return []
         offsets = np.zeros(nq + 1, dtype=np.int64)
         offsets[1:] = np.cumsum([len(a) for a in arrs])
-        pcm = _host_concat(arrs, int(offsets[-1]))
+        pcm = _host_concat(arrs, int(offsets[-1]), dtype=arrs[0].dtype)
         rows = self._row_buf(nq)
         nrows = np.zeros(nq, dtype=np.int32)
-        check(self._lib.aid_query_pcm(self._h, _p(pcm), _p(offsets), nq, AID_PCM_HOST, rows.ctypes.data,
-                                      _p(nrows), None))
+        check(self._fn("aid_query_pcm", fmt)(self._h, _p(pcm), _p(offsets), nq, AID_PCM_HOST, rows.ctypes.data,
+                                             _p(nrows), None))
         self.n_clips = nq
         return self._rows(rows, nrows, nq)
 
-    def query_pcm_submit(self, clips: Sequence[np.ndarray]) -> "PendingQuery":
+    def query_pcm_submit(self, clips: Sequence[np.ndarray], fmt: str = "f32") -> "PendingQuery":
         """query_pcm in two halves (aid_query_pcm_submit): the batch is laid into a page-locked buffer of its own,
         its copy, extraction, K5 and result copies are queued, and a PendingQuery is returned at once; collect()
         waits and returns the rows (the buffer is reused after that). A caller submits batch N + 1 before it
         collects batch N (QueryCoalescer's pipelined dispatch)."""
-        arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
+        arrs = _host_clips(clips, fmt)
         nq = len(arrs)
         offsets = np.zeros(nq + 1, dtype=np.int64)
         if nq:
@@ -606,10 +638,10 @@ class Engine:
         with self._slot_lock:
             slot = self._free_slots.pop() if self._free_slots else _new_slot()
         try:
-            pcm = _host_concat(arrs, int(offsets[-1]), slot)
+            pcm = _host_concat(arrs, int(offsets[-1]), slot, dtype=arrs[0].dtype if arrs else np.float32)
             t = ctypes.c_void_p()
-            check(self._lib.aid_query_pcm_submit(self._h, _p(pcm), _p(offsets), nq, AID_PCM_HOST, None,
-                                                 ctypes.byref(t)))
+            check(self._fn("aid_query_pcm_submit", fmt)(self._h, _p(pcm), _p(offsets), nq, AID_PCM_HOST, None,
+                                                        ctypes.byref(t)))
         except BaseException:
             self._put_slot(slot)  # a failed submit has drained its copy (drain_host_copy)
             raise
@@ -620,8 +652,10 @@ class Engine:
             if len(self._free_slots) < 4:
                 self._free_slots.append(slot)
 
-    def query_windows(self, pcm_ptr: int, starts, ends, stream: int | None = None) -> list[np.ndarray]:
-        """Extract + match device-PCM windows [starts[c], ends[c]) (may overlap) in one engine call."""
+    def query_windows(self, pcm_ptr: int, starts, ends, stream: int | None = None,
+                      fmt: str = "f32") -> list[np.ndarray]:
+        """Extract + match device-PCM windows [starts[c], ends[c]) (may overlap) in one engine call; the bounds
+        count samples of `fmt`."""
         st = np.ascontiguousarray(starts, dtype=np.int64)
         en = np.ascontiguousarray(ends, dtype=np.int64)
         nq = len(st)
@@ -629,19 +663,22 @@ class Engine:
             return []
         rows = self._row_buf(nq)
         nrows = np.zeros(nq, dtype=np.int32)
-        check(self._lib.aid_query_windows(self._h, ctypes.c_void_p(pcm_ptr), _p(st), _p(en), nq, rows.ctypes.data,
-                                          _p(nrows), ctypes.c_void_p(stream) if stream else None))
+        check(self._fn("aid_query_windows", fmt)(self._h, ctypes.c_void_p(pcm_ptr), _p(st), _p(en), nq,
+                                                 rows.ctypes.data, _p(nrows),
+                                                 ctypes.c_void_p(stream) if stream else None))
         self.n_clips = nq
         return self._rows(rows, nrows, nq)
 
-    def query_windows_submit(self, pcm_ptr: int, starts, ends, stream: int | None = None) -> "PendingQuery":
+    def query_windows_submit(self, pcm_ptr: int, starts, ends, stream: int | None = None,
+                             fmt: str = "f32") -> "PendingQuery":
         """query_windows in two halves (aid_query_windows_submit): the extraction, K5 and the result copies are queued
         on `stream` and a PendingQuery is returned at once; its collect() waits for them and returns the rows."""
         st = np.ascontiguousarray(starts, dtype=np.int64)
         en = np.ascontiguousarray(ends, dtype=np.int64)
         t = ctypes.c_void_p()
-        check(self._lib.aid_query_windows_submit(self._h, ctypes.c_void_p(pcm_ptr), _p(st), _p(en), len(st),
-                                                 ctypes.c_void_p(stream) if stream else None, ctypes.byref(t)))
+        check(self._fn("aid_query_windows_submit", fmt)(self._h, ctypes.c_void_p(pcm_ptr), _p(st), _p(en), len(st),
+                                                        ctypes.c_void_p(stream) if stream else None,
+                                                        ctypes.byref(t)))
         return PendingQuery(self, t, len(st))
 
     # -- batched exact lane --
@@ -649,19 +686,20 @@ class Engine:
                             ("confidence", "<f8")])
 
     def exact_lane(self, clips: Sequence[np.ndarray] | None = None, max_out: int = 0, *, pcm_ptr: int = 0,
-                   offsets: np.ndarray | None = None) -> list[np.ndarray]:
+                   offsets: np.ndarray | None = None, fmt: str = "f32") -> list[np.ndarray]:
         """Sub-window fan-out + match + consensus + ranking for a batch of clips (aid_exact_lane).
 
         Host clips, or device PCM (pcm_ptr) with host offsets. Returns per clip a structured array
         (track, aligned_hashes, offset_seconds, confidence) in rank order, at most max_out rows
         (default 3 x max_results: every candidate the consensus can keep)."""
         max_out = int(max_out) or 3 * self.max_results
+        fn = self._fn("aid_exact_lane", fmt)
         if clips is not None:
-            arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
+            arrs = _host_clips(clips, fmt)
             offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
             if arrs:
                 offsets[1:] = np.cumsum([len(a) for a in arrs])
-            pcm = _host_concat(arrs, int(offsets[-1]))
+            pcm = _host_concat(arrs, int(offsets[-1]), dtype=arrs[0].dtype if arrs else np.float32)
             src, loc = _p(pcm), AID_PCM_HOST
         else:
             offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -671,7 +709,7 @@ class Engine:
             return []
         out = np.zeros(n * max_out, dtype=self.EXACT_DTYPE)
         nout = np.zeros(n, dtype=np.int32)
-        check(self._lib.aid_exact_lane(self._h, src, _p(offsets), n, loc, max_out, _p(out), _p(nout), None))
+        check(fn(self._h, src, _p(offsets), n, loc, max_out, _p(out), _p(nout), None))
         # per-clip views of the one result array (4096 per-clip copies took ~3.5 ms of host time per lane call)
         return [r[:k] for r, k in zip(out.reshape(n, max_out), nout.tolist())]
 

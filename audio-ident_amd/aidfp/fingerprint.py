@@ -101,6 +101,18 @@ def db_path() -> Path:
     return Path(os.environ.get("AIDFP_DB") or os.environ.get("OLAF_DB") or DEFAULT_DB)
 
 
+PCM_FORMATS = ("f32", "s16")
+
+
+def resolve_pcm_format(name: str | None = None) -> str:
+    """The PCM format of the request bytes: `name`, else env AIDFP_PCM_FORMAT, else "f32" (the reference
+    boundary's f32le). "s16" = native int16 (s16le), what WAV data and capture devices carry: x = q / 32768."""
+    fmt = name or os.environ.get("AIDFP_PCM_FORMAT") or "f32"
+    if fmt not in PCM_FORMATS:
+        raise ValueError(f"unknown PCM format {fmt!r} (one of {', '.join(PCM_FORMATS)})")
+    return fmt
+
+
 class _Answered:
     """A coalesced batch answered at submit time (its engine submit failed and the synchronous path ran)."""
 
@@ -140,8 +152,13 @@ class FingerprintService:
 
     def __init__(self, db_dir: Path | None = None, device: int = -1, checkpoint_min_bytes: int = 64 << 20,
                  coalesce_window_s: float | None = None, max_batch: int = 256, max_batch_bytes: int = 64 << 20,
-                 coalesce_workers: int = 1, pipeline: bool = True, split_min: int = 16, split_parts: int = 2):
+                 coalesce_workers: int = 1, pipeline: bool = True, split_min: int = 16, split_parts: int = 2,
+                 pcm_format: str | None = None):
         self.db_dir = Path(db_dir) if db_dir is not None else db_path()
+        # one format per service (default: env AIDFP_PCM_FORMAT, else "f32"): the coalescer merges concurrent
+        # requests into one engine call, so formats cannot mix inside a service. The index is the same either way
+        self.pcm_format = resolve_pcm_format(pcm_format)
+        self._fmt_kw = {} if self.pcm_format == "f32" else {"fmt": self.pcm_format}
         self.device = device
         self._rw = RWLock()  # index writers exclusive, queries shared
         self._init_lock = threading.Lock()  # first-use engine creation + index load
@@ -260,9 +277,15 @@ class FingerprintService:
                 tmp.unlink(missing_ok=True)
 
     @staticmethod
-    def _pcm(buf: bytes) -> np.ndarray:
-        # a read-only float32 view of the request bytes (no copy; the engine call copies once into its batch)
+    def _pcm(buf: bytes, fmt: str = "f32") -> np.ndarray:
+        # a read-only view of the request bytes as whole samples, float32 or int16 (no copy; the engine call copies
+        # once into its batch)
+        if fmt == "s16":
+            return np.frombuffer(buf, dtype="<i2", count=len(buf) // 2).astype(np.int16, copy=False)
         return np.frombuffer(buf, dtype="<f4", count=len(buf) // 4).astype(np.float32, copy=False)
+
+    def _clip(self, buf: bytes) -> np.ndarray:
+        return self._pcm(buf, self.pcm_format)
 
     # -- operations (blocking; call from a worker thread) --
     def index_track(self, pcm: bytes, name: str) -> bool:
@@ -271,7 +294,7 @@ class FingerprintService:
         with self._rw.write():
             eng = self._eng()
             try:
-                recs = eng.extract_host([self._pcm(pcm)])[0]
+                recs = eng.extract_host([self._clip(pcm)], **self._fmt_kw)[0]
                 tid = self._next
                 # the new postings first, the journal entry, then the old ones go: a failed
                 # append leaves the previous fingerprints of `name` live
@@ -334,7 +357,7 @@ class FingerprintService:
         from ._lib import EngineError
 
         try:
-            return eng.query_pcm([self._pcm(p) for p in pcms])
+            return eng.query_pcm([self._clip(p) for p in pcms], **self._fmt_kw)
         except EngineError as exc:
             return self._rows_after_failure(eng, pcms, exc)
 
@@ -386,7 +409,8 @@ class FingerprintService:
         try:
             eng = self._eng()
             try:
-                return _PendingBatch(self, eng, pcms, eng.query_pcm_submit([self._pcm(p) for p in pcms]))
+                return _PendingBatch(self, eng, pcms,
+                                     eng.query_pcm_submit([self._clip(p) for p in pcms], **self._fmt_kw))
             except EngineError as exc:  # answered now (bisecting a batch-dependent failure)
                 out = self._matches(eng, self._rows_after_failure(eng, pcms, exc))
         except BaseException:
@@ -402,9 +426,9 @@ class FingerprintService:
 
         with self._rw.read():
             eng = self._eng()
-            pcms = [self._pcm(c) for c in clips]
+            pcms = [self._clip(c) for c in clips]
             try:
-                rows = eng.exact_lane(pcms)
+                rows = eng.exact_lane(pcms, **self._fmt_kw)
             except EngineError as exc:
                 logger.error("aidfp exact lane failed: %s", exc)
                 return [[] for _ in clips]

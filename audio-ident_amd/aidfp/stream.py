@@ -182,12 +182,22 @@ class StreamBank:
     windows in place from the streams' mono buffers, then K5).
     The reference's equivalent is one ffmpeg process and one `olaf_c query` per recorded clip
     (audio-ident-ui AudioRecorder.svelte:86-106 -> app/audio/decode.py:41-60 -> app/audio/fingerprint.py:158-219).
+
+    pcm_format="s16": the chunks are [S, n, 2] int16 (what a capture device or a WAV delivers); the staging buffer,
+    the device copy and the K6 history hold int16 and K6 converts as it stages (FPSPEC 8), so a push moves half the
+    bytes over PCIe and out of HBM. The mono buffers and everything after K6 are the same.
     """
 
     def __init__(self, engine, n_streams: int, stream_sr: int = 48000, window_s: float = 5.0, hop_s: float = 2.5,
-                 capacity_s: float = 30.0):
+                 capacity_s: float = 30.0, pcm_format: str = "f32"):
         import torch
 
+        from .engine import _fmt_suffix
+
+        _fmt_suffix(pcm_format)  # an unknown name raises
+        self.pcm_format = pcm_format
+        self._tdtype = torch.int16 if pcm_format == "s16" else torch.float32
+        self._ndtype = np.int16 if pcm_format == "s16" else np.float32
         self.eng = engine
         self.S = int(n_streams)
         self.sr = engine.sample_rate
@@ -203,7 +213,7 @@ class StreamBank:
         # per stream (the next output's last input has not arrived). Two buffers: the next history is written while
         # the launch that reads the current one may still be queued.
         self.hcap = (self.J + 1) & ~1
-        self._hist = [torch.zeros(self.S, 2 * self.hcap, dtype=torch.float32, device="cuda") for _ in range(2)]
+        self._hist = [torch.zeros(self.S, 2 * self.hcap, dtype=self._tdtype, device="cuda") for _ in range(2)]
         self.hist_n = 0      # frames held per stream, ending at stream frame n_in
         self.mono = torch.zeros(self.S, self.cap_m, dtype=torch.float32, device="cuda")
         self._pin = None
@@ -217,21 +227,27 @@ class StreamBank:
 
     def _chunk_dev(self, chunk, n: int):
         """The chunk on the device as [S, n, 2] with (frame, channel) contiguous per stream: (tensor, stream stride in
-        floats). A device chunk is used in place (a strided slice of a longer stream tensor included)."""
+        samples). A device chunk is used in place (a strided slice of a longer stream tensor included). An s16 bank
+        takes int16 chunks only (nothing is narrowed silently); an f32 bank casts what it is given, as ever."""
         import torch
 
+        s16 = self.pcm_format == "s16"
         if isinstance(chunk, torch.Tensor):
-            t = chunk if chunk.dtype == torch.float32 else chunk.float()
+            if s16 and chunk.dtype != torch.int16:
+                raise ValueError(f'pcm_format="s16" takes int16 chunks, got {chunk.dtype}')
+            t = chunk if chunk.dtype == self._tdtype else chunk.float()
             if not t.is_cuda:
                 t = t.cuda()
-            if n > 1 and (t.stride(2) != 1 or t.stride(1) != 2 or t.stride(0) % 2 or t.data_ptr() % 8):
+            if n > 1 and (t.stride(2) != 1 or t.stride(1) != 2 or t.stride(0) % 2 or t.data_ptr() % (4 if s16 else 8)):
                 t = t.contiguous()
             return t, (t.stride(0) if self.S > 1 else 2 * n)
-        x = np.ascontiguousarray(chunk, dtype=np.float32).reshape(self.S, 2 * n)
+        if s16 and np.asarray(chunk).dtype != np.int16:
+            raise ValueError(f'pcm_format="s16" takes int16 chunks, got {np.asarray(chunk).dtype}')
+        x = np.ascontiguousarray(chunk, dtype=self._ndtype).reshape(self.S, 2 * n)
         if self._pin is None or self._pin.numel() < x.size:
-            self._pin = torch.empty(x.size, dtype=torch.float32).pin_memory()
+            self._pin = torch.empty(x.size, dtype=self._tdtype).pin_memory()
         if self._cur is None or self._cur.numel() < x.size:
-            self._cur = torch.empty(x.size, dtype=torch.float32, device="cuda")
+            self._cur = torch.empty(x.size, dtype=self._tdtype, device="cuda")
         torch.cuda.current_stream().synchronize()  # the previous chunk has left the staging buffer
         pin = self._pin[: x.size].view(self.S, 2 * n)
         pin.numpy()[:] = x
@@ -256,8 +272,8 @@ class StreamBank:
         self.hist_n = keep
 
     def push(self, chunk) -> list[list[WindowResult]]:
-        """chunk: [S, n, 2] float32 at stream_sr (device tensor or host array). Returns, per stream, the windows this
-        push completed (the same start times in every stream)."""
+        """chunk: [S, n, 2] float32 (int16 for an s16 bank) at stream_sr (device tensor or host array). Returns, per
+        stream, the windows this push completed (the same start times in every stream)."""
         return self._push(chunk, False)
 
     def push_submit(self, chunk) -> "PendingPush":
@@ -295,7 +311,8 @@ class StreamBank:
             self.eng.resample_batch_split(self._hist[0].data_ptr(), 2 * self.hcap, self.hist_n,
                                           cur.data_ptr() if n else self._hist[0].data_ptr(), cur_stride, self.S,
                                           in_base, n, 2, self.stream_sr, self.sr, self.m_next, count,
-                                          self.mono.data_ptr() + 4 * self.filled, self.cap_m, s)
+                                          self.mono.data_ptr() + 4 * self.filled, self.cap_m, s,
+                                          fmt=self.pcm_format)
             self.filled += count
             self.m_next = m_ready
         if n:

@@ -23,7 +23,7 @@
 #include "resample_design.h"
 
 namespace aid {
-void launch_stft_power(const float *pcm, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
+void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
                        int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
                        uint64_t *hot, float thr, bool keep_power, hipStream_t s);
 int peak_pick_blocks_per_cu();
@@ -35,10 +35,11 @@ void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, 
 void launch_synth(float *out, const uint32_t *tracks, const int64_t *starts, int n_clips, int64_t n, int sr,
                   int noise_a, uint32_t salt, int fmax_hz, bool envelope, const int16_t *sin_tab, hipStream_t s);
 int64_t resample_lds_floats(int up, int down, int J);
-void launch_resample(const float *src, int64_t in_base, int64_t n, int channels, int up, int down, int hl, int J,
-                     const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s, int n_streams = 1,
-                     int64_t src_stride = 0, int64_t dst_stride = 0, const float *hist = nullptr, int64_t hist_n = 0,
-                     int64_t hist_stride = 0);
+void launch_resample(const void *src, bool s16, int64_t in_base, int64_t n, int channels, int up, int down, int hl,
+                     int J, const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s,
+                     int n_streams = 1, int64_t src_stride = 0, int64_t dst_stride = 0, const void *hist = nullptr,
+                     int64_t hist_n = 0, int64_t hist_stride = 0);
+void launch_s16_to_f32(const int16_t *src, int64_t n, float *dst, hipStream_t s);
 int dedup_chunks(int64_t n_cat);
 void launch_dedup_scan(const uint32_t *cw, const int64_t *coff, const double *cdur, int64_t n_cat, const uint32_t *qw,
                        const int64_t *qoff, const double *qlo, const double *qhi, int nq, double *part_sim,
@@ -83,7 +84,7 @@ void launch_match_lds(const uint64_t *recs, const int64_t *qstart, const int64_t
                       const uint16_t *sig, const uint64_t *ranges, hipStream_t s);
 uint32_t index_keys();
 void launch_downmix(const float *in, int64_t n, float *out, hipStream_t s);
-void launch_window_gather(const float *src, const int64_t *win, int n_win, int64_t max_len, float *dst, hipStream_t s);
+void launch_window_gather(const void *src, bool s16, const int64_t *win, int n_win, int64_t max_len, float *dst, hipStream_t s);
 void launch_exact_consensus(const int32_t *rows, const int32_t *nrows, int mr, const int32_t *clip_win, int n_clips,
                             double sec, int max_out, void *out, int32_t *n_out, hipStream_t s);
 void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
@@ -630,27 +631,53 @@ int64_t aid_num_frames(const aid_engine *e, int64_t n) { return e ? num_frames(n
 
 int64_t aid_hash_capacity(const aid_engine *e, int64_t n) { return e ? hash_capacity(num_frames(n, e->cfg.hop)) : 0; }
 
-static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                          void *stream, const int64_t *ends = nullptr);
+// PCM sample format of an entry point (FPSPEC 8). The float functions and their _s16 twins funnel into one
+// implementation each, which takes the samples as const void * plus the format; offsets count samples either way
+enum PcmFmt : int { kF32 = 0, kS16 = 1 };
+static inline size_t pcm_size(PcmFmt f) { return f == kS16 ? sizeof(int16_t) : sizeof(float); }
+static inline const void *pcm_at(const void *p, PcmFmt f, int64_t i) {
+    return static_cast<const char *>(p) + i * (int64_t)pcm_size(f);
+}
+
+static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                          int32_t loc, void *stream, const int64_t *ends = nullptr);
 
 // power rows per K1 -> K2 clip group of one extraction call (3 GB of plane; extract_locked)
 constexpr int64_t kPlaneRows = (int64_t)3 << 18;
 
-int aid_extract(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc, void *stream) {
-    if (!e || !offsets || n_clips < 0) return fail(AID_ERR_INVALID, "aid_extract: bad argument");
-    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "aid_extract: bad pcm_location");
-    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, "aid_extract: null pcm");
+// the argument checks every clip-batch entry point shares (fn = its name, for the message)
+static int check_clips(const char *fn, aid_engine *e, const void *pcm, const int64_t *offsets, int32_t n_clips,
+                       int32_t loc) {
+    const std::string f(fn);
+    if (!e || !offsets || n_clips < 0) return fail(AID_ERR_INVALID, f + ": bad argument");
+    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, f + ": bad pcm_location");
     for (int c = 0; c < n_clips; ++c)
         if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
-            return fail(AID_ERR_INVALID, "aid_extract: offsets must be non-decreasing and >= 0");
+            return fail(AID_ERR_INVALID, f + ": offsets must be non-decreasing and >= 0");
+    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, f + ": null pcm");
+    return AID_OK;
+}
+
+static int extract_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
+                         int32_t n_clips, int32_t loc, void *stream) {
+    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
-    return drain_host_copy(e, loc, stream, extract_locked(e, pcm, offsets, n_clips, loc, stream));
+    return drain_host_copy(e, loc, stream, extract_locked(e, pcm, fmt, offsets, n_clips, loc, stream));
+}
+
+int aid_extract(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc, void *stream) {
+    return extract_entry("aid_extract", e, pcm, kF32, offsets, n_clips, loc, stream);
+}
+
+int aid_extract_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                    void *stream) {
+    return extract_entry("aid_extract_s16", e, pcm, kS16, offsets, n_clips, loc, stream);
 }
 
 // Clip c is pcm[offsets[c], offsets[c + 1]); with `ends` (device PCM only) it is pcm[offsets[c], ends[c]), so
 // clips may overlap (the exact lane's sub-windows are read in place).
-static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                          void *stream, const int64_t *ends) {
+static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                          int32_t loc, void *stream, const int64_t *ends) {
     if (ends && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "extract: clip ends need device PCM");
     HIP_TRY(hipSetDevice(e->device));
     auto clip_len = [&](int c) { return (ends ? ends[c] : offsets[c + 1]) - offsets[c]; };
@@ -737,7 +764,8 @@ static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offset
         while (c == gstart[g + 1]) ++g;
         if (c == gstart[g]) gfirst[g] = frames;
         if (loc == AID_PCM_DEVICE) {
-            d.pcm_off = offsets[c];  // odd: K1's float2 frame loads are then 4-byte aligned (dword alignment suffices)
+            // odd: K1's float2 frame loads are then 4-byte aligned (dword alignment suffices); s16 pairs 2-byte
+            d.pcm_off = offsets[c];
         } else {
             d.pcm_off = offsets[c] - offsets[0];  // the clips' span is staged as one copy
             staged = offsets[c] + n - offsets[0];
@@ -780,7 +808,7 @@ static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offset
     HIP_TRY(e->chunk_counts.reserve((size_t)chunks + 1));
     HIP_TRY(e->records.reserve((size_t)recs + 1));
     HIP_TRY(e->counts.reserve((size_t)n_clips + 1));
-    const float *dpcm = pcm;
+    const void *dpcm = pcm;
     if (loc == AID_PCM_HOST && staged > 0) {
         // K1 of an earlier call may still read the staging buffer: on the same stream the new copy is ordered after
         // it (a pipelined submit must not wait for the previous batch's K1), on another stream the host waits
@@ -788,8 +816,10 @@ static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offset
         e->stage_ev_live = false;
         // one copy of the clips' whole span (clips at odd offsets are read with dword-aligned float2 loads; a copy
         // per clip cost ~10-20 us of call overhead each: 64 coalesced service queries ~1 ms)
-        HIP_TRY(e->pcm_stage.reserve((size_t)staged));
-        HIP_TRY(hipMemcpyAsync(e->pcm_stage.p, pcm + offsets[0], staged * sizeof(float), hipMemcpyHostToDevice, s));
+        // the staging buffer is raw bytes to both formats (s16: half the copy); stage_ev orders its reuse across them
+        const size_t nbytes = (size_t)staged * pcm_size(fmt);
+        HIP_TRY(e->pcm_stage.reserve((nbytes + sizeof(float) - 1) / sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(e->pcm_stage.p, pcm_at(pcm, fmt, offsets[0]), nbytes, hipMemcpyHostToDevice, s));
         dpcm = e->pcm_stage.p;
     }
     if (n_clips > 0 && !desc_same) {
@@ -821,7 +851,7 @@ static int extract_locked(aid_engine *e, const float *pcm, const int64_t *offset
             if (gframes[g] == 0) continue;
             {
                 ProfScope ps(e, AID_K_STFT, s, true);
-                launch_stft_power(dpcm, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab,
+                launch_stft_power(dpcm, fmt == kS16, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab,
                                   e->power.p, false, e->hotw.p, e->cfg.peak_threshold,
                                   (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0, s);
             }
@@ -950,7 +980,7 @@ int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int6
     if (he == hipSuccess) he = hipMemcpy(d_pcm, pcm, n * sizeof(float), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_desc, &d, sizeof(ClipDesc), hipMemcpyHostToDevice);
     if (he == hipSuccess) {
-        launch_stft_power(d_pcm, d_desc, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop, e->d_tab,
+        launch_stft_power(d_pcm, false, d_desc, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop, e->d_tab,
                           d_out, true, nullptr, e->cfg.peak_threshold, true, s);
         he = hipGetLastError();
     }
@@ -1044,13 +1074,19 @@ int64_t aid_resample_len(int64_t n, int32_t sr_in, int32_t sr_out) {
     return (n * p.up + p.down - 1) / p.down;
 }
 
-static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, float **out) {
-    auto it = e->rs_taps.find({p.up, p.down});
+// impulse: the unit impulse at the filter's centre instead of the designed taps (cached under -down)
+static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse, float **out) {
+    const std::pair<int32_t, int32_t> key{p.up, impulse ? -p.down : p.down};
+    auto it = e->rs_taps.find(key);
     if (it != e->rs_taps.end()) {
         *out = it->second;
         return AID_OK;
     }
-    const std::vector<float> h = resample_phase_taps(p);
+    std::vector<float> h = resample_phase_taps(p);
+    if (impulse) {
+        std::fill(h.begin(), h.end(), 0.0f);
+        h[(size_t)(p.hl % p.up) * p.J + p.hl / p.up] = 1.0f;  // taps[k], k = phase + j * up = hl
+    }
     float *taps = nullptr;
     HIP_TRY(hipMalloc(&taps, h.size() * sizeof(float)));
     hipError_t he = hipMemcpy(taps, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -1058,7 +1094,7 @@ static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, float **out) 
         (void)hipFree(taps);
         return fail(AID_ERR_DEVICE, std::string("aid_resample: ") + hipGetErrorString(he));
     }
-    e->rs_taps[{p.up, p.down}] = taps;
+    e->rs_taps[key] = taps;
     *out = taps;
     return AID_OK;
 }
@@ -1068,25 +1104,31 @@ int aid_resample_range(aid_engine *e, const float *src, int64_t in_base, int64_t
     return aid_resample_batch(e, src, 0, 1, in_base, n, channels, sr_in, sr_out, m_first, count, dst, 0, stream);
 }
 
-static int resample_batch(aid_engine *e, const float *src, int64_t src_stride, int32_t n_streams, int64_t in_base,
-                          int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count,
-                          float *dst, int64_t dst_stride, void *stream, const float *hist, int64_t hist_n,
+// src / hist are samples of `fmt` and the strides count them; a stereo frame must be aligned to its own size
+// (8 bytes of float, 4 of s16: the kernels read it as one word)
+static int resample_batch(aid_engine *e, const void *src, PcmFmt fmt, int64_t src_stride, int32_t n_streams,
+                          int64_t in_base, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out, int64_t m_first,
+                          int64_t count, float *dst, int64_t dst_stride, void *stream, const void *hist, int64_t hist_n,
                           int64_t hist_stride) {
+    const uintptr_t frame_mask = 2 * pcm_size(fmt) - 1;
     if (!e || n < 0 || in_base < 0 || m_first < 0 || count < 0 || (channels != 1 && channels != 2) || n_streams < 0 ||
         n_streams > 65535 || src_stride < 0 || dst_stride < 0 || hist_n < 0 || hist_n > in_base || hist_stride < 0)
         return fail(AID_ERR_INVALID, "aid_resample: bad argument");
     if (n_streams > 1 && (src_stride < n * channels || dst_stride < count || (channels == 2 && (src_stride & 1))))
         return fail(AID_ERR_INVALID, "aid_resample_batch: strides must cover one stream (stereo: even)");
     if (hist_n > 0 && (!hist || (n_streams > 1 && hist_stride < hist_n * channels) ||
-                       (channels == 2 && ((hist_stride & 1) || (reinterpret_cast<uintptr_t>(hist) & 7)))))
+                       (channels == 2 && ((hist_stride & 1) || (reinterpret_cast<uintptr_t>(hist) & frame_mask)))))
         return fail(AID_ERR_INVALID, "aid_resample_batch_split: bad history (null, stride, or stereo alignment)");
     if (n_streams == 0) return AID_OK;
     ResamplePlan p;
     if (!resample_plan(sr_in, sr_out, p)) return fail(AID_ERR_INVALID, "aid_resample: sample rates must be > 0");
     if (count == 0) return AID_OK;
     if (!dst || (n > 0 && !src)) return fail(AID_ERR_INVALID, "aid_resample: null buffer");
-    if (channels == 2 && (reinterpret_cast<uintptr_t>(src) & 7))
-        return fail(AID_ERR_INVALID, "aid_resample: stereo src must be 8-byte aligned");
+    if (channels == 2 && (reinterpret_cast<uintptr_t>(src) & frame_mask))
+        return fail(AID_ERR_INVALID, fmt == kS16 ? "aid_resample: stereo s16 src must be 4-byte aligned"
+                                                 : "aid_resample: stereo src must be 8-byte aligned");
+    if (channels == 1 && fmt == kS16 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(hist)) & 1))
+        return fail(AID_ERR_INVALID, "aid_resample: s16 src must be 2-byte aligned");
     if (resample_lds_floats(p.up, p.down, p.J) * 4 > 65536)
         return fail(AID_ERR_INVALID, "aid_resample: down/up ratio too large (LDS window > 64 KB)");
     if ((int64_t)p.up * p.J > (1 << 24)) return fail(AID_ERR_INVALID, "aid_resample: tap table too large");
@@ -1094,10 +1136,13 @@ static int resample_batch(aid_engine *e, const float *src, int64_t src_stride, i
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = pick_stream(e, stream);
     float *taps = nullptr;
-    if (int rc = resample_taps_dev(e, p, &taps)) return rc;
+    // up == down copies (FPSPEC 8). Integer PCM gets exactly the copy from the same kernels through a unit-impulse
+    // table: fma(1, x, +0) = x and every other tap adds +0, and an s16 sample is never -0. The float path keeps the
+    // designed taps it has always used there (off-centre ~1e-17, not 0)
+    if (int rc = resample_taps_dev(e, p, fmt == kS16 && p.up == p.down, &taps)) return rc;
     {
         ProfScope ps(e, AID_K_RESAMPLE, s);
-        launch_resample(src, in_base, n, channels, p.up, p.down, p.hl, p.J, taps, dst, m_first, count, s, n_streams,
+        launch_resample(src, fmt == kS16, in_base, n, channels, p.up, p.down, p.hl, p.J, taps, dst, m_first, count, s, n_streams,
                         src_stride, dst_stride, hist, hist_n, hist_stride);
     }
     HIP_TRY(hipGetLastError());
@@ -1107,7 +1152,7 @@ static int resample_batch(aid_engine *e, const float *src, int64_t src_stride, i
 int aid_resample_batch(aid_engine *e, const float *src, int64_t src_stride, int32_t n_streams, int64_t in_base, int64_t n,
                        int32_t channels, int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count, float *dst,
                        int64_t dst_stride, void *stream) {
-    return resample_batch(e, src, src_stride, n_streams, in_base, n, channels, sr_in, sr_out, m_first, count, dst,
+    return resample_batch(e, src, kF32, src_stride, n_streams, in_base, n, channels, sr_in, sr_out, m_first, count, dst,
                           dst_stride, stream, nullptr, 0, 0);
 }
 
@@ -1115,12 +1160,20 @@ int aid_resample_batch_split(aid_engine *e, const float *hist, int64_t hist_stri
                              int64_t src_stride, int32_t n_streams, int64_t in_base, int64_t n, int32_t channels,
                              int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count, float *dst,
                              int64_t dst_stride, void *stream) {
-    return resample_batch(e, src, src_stride, n_streams, in_base, n, channels, sr_in, sr_out, m_first, count, dst,
+    return resample_batch(e, src, kF32, src_stride, n_streams, in_base, n, channels, sr_in, sr_out, m_first, count, dst,
                           dst_stride, stream, hist, hist_n, hist_stride);
 }
 
-int aid_resample(aid_engine *e, const float *src, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out,
-                 float *dst, int64_t cap, int64_t *n_out, void *stream) {
+int aid_resample_batch_split_s16(aid_engine *e, const int16_t *hist, int64_t hist_stride, int64_t hist_n,
+                                 const int16_t *src, int64_t src_stride, int32_t n_streams, int64_t in_base, int64_t n,
+                                 int32_t channels, int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count,
+                                 float *dst, int64_t dst_stride, void *stream) {
+    return resample_batch(e, src, kS16, src_stride, n_streams, in_base, n, channels, sr_in, sr_out, m_first, count, dst,
+                          dst_stride, stream, hist, hist_n, hist_stride);
+}
+
+static int resample_whole(aid_engine *e, const void *src, PcmFmt fmt, int64_t n, int32_t channels, int32_t sr_in,
+                          int32_t sr_out, float *dst, int64_t cap, int64_t *n_out, void *stream) {
     if (!e || n < 0 || (channels != 1 && channels != 2)) return fail(AID_ERR_INVALID, "aid_resample: bad argument");
     const int64_t m = aid_resample_len(n, sr_in, sr_out);
     if (n > 0 && m == 0) return fail(AID_ERR_INVALID, "aid_resample: sample rates must be > 0");
@@ -1131,10 +1184,26 @@ int aid_resample(aid_engine *e, const float *src, int64_t n, int32_t channels, i
         if (!src || !dst) return fail(AID_ERR_INVALID, "aid_resample: null buffer");
         std::lock_guard<std::mutex> lk(e->mu);
         HIP_TRY(hipSetDevice(e->device));
+        if (fmt == kS16) {  // the copy converts
+            if (reinterpret_cast<uintptr_t>(src) & 1) return fail(AID_ERR_INVALID, "aid_resample: s16 src must be 2-byte aligned");
+            launch_s16_to_f32(static_cast<const int16_t *>(src), n, dst, pick_stream(e, stream));
+            HIP_TRY(hipGetLastError());
+            return AID_OK;
+        }
         HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, pick_stream(e, stream)));
         return AID_OK;
     }
-    return aid_resample_range(e, src, 0, n, channels, sr_in, sr_out, 0, m, dst, stream);
+    return resample_batch(e, src, fmt, 0, 1, 0, n, channels, sr_in, sr_out, 0, m, dst, 0, stream, nullptr, 0, 0);
+}
+
+int aid_resample(aid_engine *e, const float *src, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out,
+                 float *dst, int64_t cap, int64_t *n_out, void *stream) {
+    return resample_whole(e, src, kF32, n, channels, sr_in, sr_out, dst, cap, n_out, stream);
+}
+
+int aid_resample_s16(aid_engine *e, const int16_t *src, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out,
+                     float *dst, int64_t cap, int64_t *n_out, void *stream) {
+    return resample_whole(e, src, kS16, n, channels, sr_in, sr_out, dst, cap, n_out, stream);
 }
 
 }  // extern "C"
@@ -2398,21 +2467,26 @@ int aid_query_extracted(aid_engine *e, aid_match_row *rows, int32_t *nrows) {
     return query_extracted_locked(e, rows, nrows);
 }
 
-int aid_query_pcm(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                  aid_match_row *rows, int32_t *nrows, void *stream) {
-    if (!e || !offsets || n_clips < 0) return fail(AID_ERR_INVALID, "aid_query_pcm: bad argument");
-    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "aid_query_pcm: bad pcm_location");
-    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, "aid_query_pcm: null pcm");
-    for (int c = 0; c < n_clips; ++c)
-        if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
-            return fail(AID_ERR_INVALID, "aid_query_pcm: offsets must be non-decreasing and >= 0");
-    if (n_clips > 0 && (!rows || !nrows)) return fail(AID_ERR_INVALID, "aid_query_pcm: null output");
+static int query_pcm_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
+                           int32_t n_clips, int32_t loc, aid_match_row *rows, int32_t *nrows, void *stream) {
+    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
+    if (n_clips > 0 && (!rows || !nrows)) return fail(AID_ERR_INVALID, std::string(fn) + ": null output");
     if (n_clips == 0) return AID_OK;
     // one critical section: no other thread's extraction can land between this batch's K1-K3 and K5
     std::lock_guard<std::mutex> lk(e->mu);
     if (int rc = ensure_index(e)) return rc;
-    if (int rc = extract_locked(e, pcm, offsets, n_clips, loc, stream)) return drain_host_copy(e, loc, stream, rc);
+    if (int rc = extract_locked(e, pcm, fmt, offsets, n_clips, loc, stream)) return drain_host_copy(e, loc, stream, rc);
     return drain_host_copy(e, loc, stream, query_extracted_locked(e, rows, nrows));
+}
+
+int aid_query_pcm(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                  aid_match_row *rows, int32_t *nrows, void *stream) {
+    return query_pcm_entry("aid_query_pcm", e, pcm, kF32, offsets, n_clips, loc, rows, nrows, stream);
+}
+
+int aid_query_pcm_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                      aid_match_row *rows, int32_t *nrows, void *stream) {
+    return query_pcm_entry("aid_query_pcm_s16", e, pcm, kS16, offsets, n_clips, loc, rows, nrows, stream);
 }
 
 // ---- asynchronous windowed query: submit enqueues the extraction, K5's LDS path and the result
@@ -2454,14 +2528,14 @@ static aid_query_ticket *take_ticket(aid_engine *e) {
 
 // the body both submit entries share (engine lock held): the extraction of n clips, K5's LDS pass over the ticket's
 // own copy of the records, the result copies into its page-locked buffers and its event
-static int submit_locked(aid_engine *e, const float *pcm, const int64_t *offsets, const int64_t *ends, int32_t n,
-                         int32_t loc, void *stream, aid_query_ticket *t) {
+static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, const int64_t *ends,
+                         int32_t n, int32_t loc, void *stream, aid_query_ticket *t) {
     t->nq = n;
     t->nrec = 0;
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_index(e)) return rc;
     if (n == 0) return AID_OK;
-    if (int rc = extract_locked(e, pcm, offsets, n, loc, stream, ends)) return rc;
+    if (int rc = extract_locked(e, pcm, fmt, offsets, n, loc, stream, ends)) return rc;
     if (int rc = check_query_frames(e)) return rc;
     hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
     t->s = s;
@@ -2499,39 +2573,54 @@ static int submit_locked(aid_engine *e, const float *pcm, const int64_t *offsets
     return AID_OK;
 }
 
-extern "C" int aid_query_windows_submit(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends,
-                                        int32_t n_windows, void *stream, aid_query_ticket **out) {
+static int windows_submit_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *starts,
+                                const int64_t *ends, int32_t n_windows, void *stream, aid_query_ticket **out) {
     if (!e || n_windows < 0 || !out || (n_windows > 0 && (!starts || !ends || !pcm)))
-        return fail(AID_ERR_INVALID, "aid_query_windows_submit: bad argument");
+        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
     *out = nullptr;
     for (int c = 0; c < n_windows; ++c)
-        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, "aid_query_windows_submit: bad window");
+        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, std::string(fn) + ": bad window");
     std::lock_guard<std::mutex> lk(e->mu);
     std::unique_ptr<aid_query_ticket> t(take_ticket(e));
-    if (int rc = submit_locked(e, pcm, starts, ends, n_windows, AID_PCM_DEVICE, stream, t.get())) return rc;
+    if (int rc = submit_locked(e, pcm, fmt, starts, ends, n_windows, AID_PCM_DEVICE, stream, t.get())) return rc;
     *out = t.release();
     return AID_OK;
 }
 
+extern "C" int aid_query_windows_submit(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends,
+                                        int32_t n_windows, void *stream, aid_query_ticket **out) {
+    return windows_submit_entry("aid_query_windows_submit", e, pcm, kF32, starts, ends, n_windows, stream, out);
+}
+
+extern "C" int aid_query_windows_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts,
+                                            const int64_t *ends, int32_t n_windows, void *stream,
+                                            aid_query_ticket **out) {
+    return windows_submit_entry("aid_query_windows_submit_s16", e, pcm, kS16, starts, ends, n_windows, stream, out);
+}
+
 // aid_query_pcm in two halves (the query coalescer's pipelined batches): host PCM must stay unchanged until the ticket
 // is collected (its one H2D copy is queued, not waited for)
-extern "C" int aid_query_pcm_submit(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips,
-                                    int32_t loc, void *stream, aid_query_ticket **out) {
-    if (!e || !offsets || n_clips < 0 || !out) return fail(AID_ERR_INVALID, "aid_query_pcm_submit: bad argument");
+static int pcm_submit_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
+                            int32_t n_clips, int32_t loc, void *stream, aid_query_ticket **out) {
+    if (!out) return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
     *out = nullptr;
-    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE)
-        return fail(AID_ERR_INVALID, "aid_query_pcm_submit: bad pcm_location");
-    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0])
-        return fail(AID_ERR_INVALID, "aid_query_pcm_submit: null pcm");
-    for (int c = 0; c < n_clips; ++c)
-        if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
-            return fail(AID_ERR_INVALID, "aid_query_pcm_submit: offsets must be non-decreasing and >= 0");
+    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
     std::unique_ptr<aid_query_ticket> t(take_ticket(e));
-    if (int rc = submit_locked(e, pcm, offsets, nullptr, n_clips, loc, stream, t.get()))
+    if (int rc = submit_locked(e, pcm, fmt, offsets, nullptr, n_clips, loc, stream, t.get()))
         return drain_host_copy(e, loc, stream, rc);
     *out = t.release();
     return AID_OK;
+}
+
+extern "C" int aid_query_pcm_submit(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips,
+                                    int32_t loc, void *stream, aid_query_ticket **out) {
+    return pcm_submit_entry("aid_query_pcm_submit", e, pcm, kF32, offsets, n_clips, loc, stream, out);
+}
+
+extern "C" int aid_query_pcm_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
+                                        int32_t loc, void *stream, aid_query_ticket **out) {
+    return pcm_submit_entry("aid_query_pcm_submit_s16", e, pcm, kS16, offsets, n_clips, loc, stream, out);
 }
 
 extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid_match_row *rows, int32_t *nrows) {
@@ -2609,19 +2698,30 @@ extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid
     return AID_OK;
 }
 
-int aid_query_windows(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends, int32_t n_windows,
-                      aid_match_row *rows, int32_t *nrows, void *stream) {
+static int query_windows_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *starts,
+                               const int64_t *ends, int32_t n_windows, aid_match_row *rows, int32_t *nrows,
+                               void *stream) {
     if (!e || n_windows < 0 || (n_windows > 0 && (!starts || !ends || !rows || !nrows)))
-        return fail(AID_ERR_INVALID, "aid_query_windows: bad argument");
+        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
     for (int c = 0; c < n_windows; ++c)
-        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, "aid_query_windows: bad window");
-    if (n_windows > 0 && !pcm) return fail(AID_ERR_INVALID, "aid_query_windows: null pcm");
+        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, std::string(fn) + ": bad window");
+    if (n_windows > 0 && !pcm) return fail(AID_ERR_INVALID, std::string(fn) + ": null pcm");
     if (n_windows == 0) return AID_OK;
     // one critical section, as aid_query_pcm: K1 reads every window in place (they may overlap), then K5
     std::lock_guard<std::mutex> lk(e->mu);
     if (int rc = ensure_index(e)) return rc;
-    if (int rc = extract_locked(e, pcm, starts, n_windows, AID_PCM_DEVICE, stream, ends)) return rc;
+    if (int rc = extract_locked(e, pcm, fmt, starts, n_windows, AID_PCM_DEVICE, stream, ends)) return rc;
     return query_extracted_locked(e, rows, nrows);
+}
+
+int aid_query_windows(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends, int32_t n_windows,
+                      aid_match_row *rows, int32_t *nrows, void *stream) {
+    return query_windows_entry("aid_query_windows", e, pcm, kF32, starts, ends, n_windows, rows, nrows, stream);
+}
+
+int aid_query_windows_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts, const int64_t *ends,
+                          int32_t n_windows, aid_match_row *rows, int32_t *nrows, void *stream) {
+    return query_windows_entry("aid_query_windows_s16", e, pcm, kS16, starts, ends, n_windows, rows, nrows, stream);
 }
 
 }  // extern "C"
@@ -2665,26 +2765,34 @@ extern "C" int aid_exact_windows(int64_t n, int32_t sample_rate, int64_t *lo, in
     return 3;
 }
 
-static int exact_lane_locked(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                             int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream);
+static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream);
+
+static int exact_lane_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
+                            int32_t n_clips, int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out,
+                            void *stream) {
+    if (!e || !offsets || n_clips < 0 || max_out <= 0 || (n_clips > 0 && (!out || !n_out)))
+        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
+    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
+    if (e->cfg.max_results > 256) return fail(AID_ERR_INVALID, std::string(fn) + ": engine max_results must be <= 256");
+    if (n_clips == 0) return AID_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return drain_host_copy(e, loc, stream,
+                           exact_lane_locked(e, pcm, fmt, offsets, n_clips, loc, max_out, out, n_out, stream));
+}
 
 extern "C" int aid_exact_lane(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
                               int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
-    if (!e || !offsets || n_clips < 0 || max_out <= 0 || (n_clips > 0 && (!out || !n_out)))
-        return fail(AID_ERR_INVALID, "aid_exact_lane: bad argument");
-    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "aid_exact_lane: bad pcm_location");
-    for (int c = 0; c < n_clips; ++c)
-        if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
-            return fail(AID_ERR_INVALID, "aid_exact_lane: offsets must be non-decreasing and >= 0");
-    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, "aid_exact_lane: null pcm");
-    if (e->cfg.max_results > 256) return fail(AID_ERR_INVALID, "aid_exact_lane: engine max_results must be <= 256");
-    if (n_clips == 0) return AID_OK;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return drain_host_copy(e, loc, stream, exact_lane_locked(e, pcm, offsets, n_clips, loc, max_out, out, n_out, stream));
+    return exact_lane_entry("aid_exact_lane", e, pcm, kF32, offsets, n_clips, loc, max_out, out, n_out, stream);
 }
 
-static int exact_lane_locked(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                             int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
+extern "C" int aid_exact_lane_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
+                                  int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
+    return exact_lane_entry("aid_exact_lane_s16", e, pcm, kS16, offsets, n_clips, loc, max_out, out, n_out, stream);
+}
+
+static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_index(e)) return rc;
     hipStream_t s = pick_stream(e, stream);
@@ -2720,11 +2828,12 @@ static int exact_lane_locked(aid_engine *e, const float *pcm, const int64_t *off
         clipwin[3 * c + 2] = mode;
     }
     const int n_win = (int)(xoff.size() - 1);
-    const float *src = pcm + offsets[0];
+    const void *src = pcm_at(pcm, fmt, offsets[0]);
     if (loc == AID_PCM_HOST) {
         const int64_t n_all = offsets[n_clips] - offsets[0];
-        HIP_TRY(e->x_in.reserve((size_t)std::max<int64_t>(n_all, 1)));
-        if (n_all > 0) HIP_TRY(hipMemcpyAsync(e->x_in.p, src, n_all * sizeof(float), hipMemcpyHostToDevice, s));
+        const size_t nbytes = (size_t)n_all * pcm_size(fmt);  // x_in is raw bytes to both formats
+        HIP_TRY(e->x_in.reserve(std::max<size_t>((nbytes + sizeof(float) - 1) / sizeof(float), 1)));
+        if (n_all > 0) HIP_TRY(hipMemcpyAsync(e->x_in.p, src, nbytes, hipMemcpyHostToDevice, s));
         src = e->x_in.p;
     }
     HIP_TRY(e->x_clipwin.reserve(clipwin.size()));
@@ -2738,11 +2847,12 @@ static int exact_lane_locked(aid_engine *e, const float *pcm, const int64_t *off
             HIP_TRY(e->x_wdesc.reserve(wdesc.size()));
             HIP_TRY(hipMemcpyAsync(e->x_wdesc.p, wdesc.data(), wdesc.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
             HIP_TRY(e->x_win.reserve((size_t)std::max<int64_t>(staged, 2)));
-            launch_window_gather(src, e->x_wdesc.p, n_win, max_len, e->x_win.p, s);
+            // the gather converts s16 windows on the way: the staged windows are float to either format
+            launch_window_gather(src, fmt == kS16, e->x_wdesc.p, n_win, max_len, e->x_win.p, s);
             HIP_TRY(hipGetLastError());
-            if (int rc = extract_locked(e, e->x_win.p, xoff.data(), n_win, AID_PCM_DEVICE, s)) return rc;
+            if (int rc = extract_locked(e, e->x_win.p, kF32, xoff.data(), n_win, AID_PCM_DEVICE, s)) return rc;
         } else {
-            if (int rc = extract_locked(e, src, wstart.data(), n_win, AID_PCM_DEVICE, s, wend.data())) return rc;
+            if (int rc = extract_locked(e, src, fmt, wstart.data(), n_win, AID_PCM_DEVICE, s, wend.data())) return rc;
         }
         if (int rc = check_query_frames(e)) return rc;
         HIP_TRY(e->q_start.reserve(n_win));

@@ -27,6 +27,20 @@ struct ExactRow {  // == aid_exact_row (include/aidfp.h)
     double confidence;
 };
 
+// s16 windows (integer PCM, FPSPEC 8) are converted here, x = float(q) * 2^-15 (exact): the staged windows are float
+__global__ __launch_bounds__(256) void k_window_gather_s16(const int16_t *__restrict__ src,
+                                                           const int64_t *__restrict__ win, int n_win,
+                                                           float *__restrict__ dst) {
+    for (int w = blockIdx.y; w < n_win; w += gridDim.y) {
+        const int64_t so = win[3 * w], n2 = win[3 * w + 1] >> 1, d = win[3 * w + 2];
+        float2 *__restrict__ d2 = reinterpret_cast<float2 *>(dst + d);
+        const int16_t *s = src + so;
+        const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+        for (int64_t i = i0; i < n2; i += step)
+            d2[i] = make_float2((float)s[2 * i] * 0x1p-15f, (float)s[2 * i + 1] * 0x1p-15f);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_window_gather(const float *__restrict__ src, const int64_t *__restrict__ win,
                                                        int n_win, float *__restrict__ dst) {
     // win[3*w] = source offset, win[3*w+1] = length (even), win[3*w+2] = destination offset (even): float2
@@ -150,12 +164,16 @@ __global__ __launch_bounds__(256) void k_rows_scatter(const int32_t *__restrict_
     }
 }
 
-void launch_window_gather(const float *src, const int64_t *win, int n_win, int64_t max_len, float *dst, hipStream_t s) {
+void launch_window_gather(const void *src, bool s16, const int64_t *win, int n_win, int64_t max_len, float *dst,
+                          hipStream_t s) {
     if (n_win <= 0 || max_len <= 0) return;
     int64_t bx = (max_len + 1023) / 1024;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(k_window_gather, dim3((unsigned)bx, (unsigned)(n_win < 65535 ? n_win : 65535)), dim3(256), 0, s,
-                       src, win, n_win, dst);
+    const dim3 g((unsigned)bx, (unsigned)(n_win < 65535 ? n_win : 65535));
+    if (s16)
+        hipLaunchKernelGGL(k_window_gather_s16, g, dim3(256), 0, s, static_cast<const int16_t *>(src), win, n_win, dst);
+    else
+        hipLaunchKernelGGL(k_window_gather, g, dim3(256), 0, s, static_cast<const float *>(src), win, n_win, dst);
 }
 
 void launch_exact_consensus(const int32_t *rows, const int32_t *nrows, int mr, const int32_t *clip_win, int n_clips,

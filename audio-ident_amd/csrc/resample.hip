@@ -21,12 +21,20 @@ constexpr int kResMaxLdsTaps = 12288;  // floats (48 KB): larger tables are read
 // The input of one launch: stream frames [b_base, b_base + b_n) at b + y * b_stride and, optionally, the frames
 // [a_base, a_base + a_n) just before them at a + y * a_stride (y = stream of a batch), so a live stream's chunk is read
 // where its caller left it and only the last few frames of the previous chunk are kept (StreamBank); 0 elsewhere
-struct ResIn {
-    const float *a;
+// T = the input's sample type: float, or int16_t (integer PCM, FPSPEC 8: x = float(q) * 2^-15, exact); strides count T
+template <typename T>
+struct ResInT {
+    const T *a;
     int64_t a_base, a_n, a_stride;
-    const float *b;
+    const T *b;
     int64_t b_base, b_n, b_stride;
 };
+typedef ResInT<float> ResIn;
+
+// s16 -> FPSPEC sample value; the stereo downmix is (xL + xR) * 0.5f on the converted values, as for float input
+__device__ __forceinline__ float s16_val(int16_t q) { return (float)q * 0x1p-15f; }
+__device__ __forceinline__ float s16_lo(uint32_t w) { return s16_val((int16_t)(w & 0xFFFFu)); }
+__device__ __forceinline__ float s16_hi(uint32_t w) { return (float)((int32_t)w >> 16) * 0x1p-15f; }
 
 // Stage input samples lo .. lo + cnt - 1 (stream indices) into sx[0 .. cnt), downmixed at load time. The loads go out
 // kStageBatch at a time before their LDS stores: a plain strided loop waits for each load before the next (its trip
@@ -35,14 +43,16 @@ struct ResIn {
 #define AID_K6_STAGE_BATCH 8
 #endif
 constexpr int kStageBatch = AID_K6_STAGE_BATCH;
-template <bool STEREO>
-__device__ __forceinline__ void stage_window(const ResIn &in, int64_t lo, int cnt, float *sx, int tid, int nthreads) {
+template <bool STEREO, typename T>
+__device__ __forceinline__ void stage_window(const ResInT<T> &in, int64_t lo, int cnt, float *sx, int tid, int nthreads) {
+    constexpr bool S16 = sizeof(T) == 2;
     const int64_t y = blockIdx.y;
-    const float *A = in.a + y * in.a_stride, *B = in.b + y * in.b_stride;
+    const T *A = in.a + y * in.a_stride, *B = in.b + y * in.b_stride;
     // a window wholly inside part B whose 16-B words are all in it (B 16-B aligned): 16-B loads, two stereo frames or
     // four mono samples each. The hardware moved ~3.3 TB/s on 8-B lane loads of the 256-stream push (77 % of K6's
     // wave cycles waiting, every fetched byte needed) and 22 % more on 16-B ones (profiles/r06yz_k6_v4_ab.txt)
-    constexpr int kPer = STEREO ? 2 : 4;  // stream samples per 16-B word
+    // (s16: four stereo frames or eight mono samples per word, converted and downmixed here: LDS holds f32 mono)
+    constexpr int kPer = (STEREO ? 2 : 4) * (S16 ? 2 : 1);  // stream samples per 16-B word
     const int64_t k0 = lo - in.b_base;
 #if defined(AID_K6_NO_V4)  // diagnostic A/B build: 8-B / 4-B loads only
     if (false) {
@@ -51,6 +61,34 @@ __device__ __forceinline__ void stage_window(const ResIn &in, int64_t lo, int cn
 #endif
         const int64_t p0 = k0 / kPer;
         const int np = (int)((k0 + cnt - 1) / kPer - p0 + 1);
+        if constexpr (S16) {
+            const uint4 *B4 = reinterpret_cast<const uint4 *>(B);
+            for (int i0 = tid; i0 < np; i0 += kStageBatch * nthreads) {
+                uint4 v[kStageBatch];
+#pragma unroll
+                for (int u = 0; u < kStageBatch; ++u) {
+                    const int i = i0 + u * nthreads;
+                    v[u] = i < np ? B4[p0 + i] : make_uint4(0u, 0u, 0u, 0u);
+                }
+#pragma unroll
+                for (int u = 0; u < kStageBatch; ++u) {
+                    const int i = i0 + u * nthreads;
+                    if (i >= np) continue;
+                    const int f = (int)(kPer * (p0 + i) - k0);  // window index of the word's first sample
+                    const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if constexpr (STEREO) {
+                            if (f + j >= 0 && f + j < cnt) sx[f + j] = (s16_lo(w[j]) + s16_hi(w[j])) * 0.5f;
+                        } else {
+                            if (f + 2 * j >= 0 && f + 2 * j < cnt) sx[f + 2 * j] = s16_lo(w[j]);
+                            if (f + 2 * j + 1 >= 0 && f + 2 * j + 1 < cnt) sx[f + 2 * j + 1] = s16_hi(w[j]);
+                        }
+                    }
+                }
+            }
+            return;
+        }
         const float4 *B4 = reinterpret_cast<const float4 *>(B);
         for (int i0 = tid; i0 < np; i0 += kStageBatch * nthreads) {
             float4 v[kStageBatch];
@@ -83,7 +121,7 @@ __device__ __forceinline__ void stage_window(const ResIn &in, int64_t lo, int cn
         for (int u = 0; u < kStageBatch; ++u) {
             const int i = i0 + u * nthreads;
             const int64_t g = lo + i;
-            const float *p = nullptr;
+            const T *p = nullptr;
             int64_t k = 0;
             if (i < cnt) {
                 if (g >= in.b_base && g - in.b_base < in.b_n) {
@@ -96,7 +134,12 @@ __device__ __forceinline__ void stage_window(const ResIn &in, int64_t lo, int cn
             }
             v[u] = 0.0f;
             if (p) {
-                if constexpr (STEREO) {
+                if constexpr (S16 && STEREO) {  // one frame = one dword (the engine checks the 4-byte alignment)
+                    const uint32_t w = reinterpret_cast<const uint32_t *>(p)[k];
+                    v[u] = (s16_lo(w) + s16_hi(w)) * 0.5f;
+                } else if constexpr (S16) {
+                    v[u] = s16_val(p[k]);
+                } else if constexpr (STEREO) {
                     const float2 s = reinterpret_cast<const float2 *>(p)[k];
                     v[u] = (s.x + s.y) * 0.5f;
                 } else {
@@ -112,8 +155,8 @@ __device__ __forceinline__ void stage_window(const ResIn &in, int64_t lo, int cn
 
 // MODE 0: taps from L1/L2, 1: taps staged in LDS, 2: integer decimation (up == 1): one phase,
 // the taps are wave-uniform and read as scalar loads (no LDS traffic for them)
-template <bool STEREO, int MODE>
-__global__ __launch_bounds__(kResThreads) void k_resample(ResIn in, int up, int down, int hl, int J,
+template <bool STEREO, int MODE, typename T = float>
+__global__ __launch_bounds__(kResThreads) void k_resample(ResInT<T> in, int up, int down, int hl, int J,
                                                          const float *__restrict__ taps, float *__restrict__ dst,
                                                          int64_t m_first, int64_t m_end, int64_t dst_stride) {
     // Outputs m_first .. m_end-1 (stream indices) go to dst[m - m_first].
@@ -168,8 +211,8 @@ constexpr int kDecThreads = 256;
 template <int DOWN, int J>
 constexpr int dec_window() { return (kDecThreads * kDecR - 1) * DOWN + J; }
 
-template <bool STEREO, int DOWN, int J>
-__global__ __launch_bounds__(kDecThreads) void k_decimate(ResIn in, int hl, const float *__restrict__ taps,
+template <bool STEREO, int DOWN, int J, typename T = float>
+__global__ __launch_bounds__(kDecThreads) void k_decimate(ResInT<T> in, int hl, const float *__restrict__ taps,
                                                           float *__restrict__ dst, int64_t m_first, int64_t m_end,
                                                           int64_t dst_stride) {
     static_assert((kDecR * DOWN) % 4 == 0, "a thread's run must start 16-B aligned in LDS");
@@ -225,8 +268,8 @@ __global__ __launch_bounds__(kDecThreads) void k_decimate(ResIn in, int hl, cons
 // rows (which also bank-conflicted). Same fma chain per output (taps j = 0..J-1 in order).
 constexpr int kResR = 16;  // outputs per thread (one phase)
 
-template <bool STEREO>
-__global__ __launch_bounds__(256) void k_resample_phase(ResIn in, int up, int down, int hl, int J,
+template <bool STEREO, typename T = float>
+__global__ __launch_bounds__(256) void k_resample_phase(ResInT<T> in, int up, int down, int hl, int J,
                                                        const float *__restrict__ taps, float *__restrict__ dst,
                                                        int64_t m_first, int64_t m_end, int64_t dst_stride) {
     dst += (int64_t)blockIdx.y * dst_stride;  // stream of a batch (k_resample)
@@ -285,23 +328,24 @@ int64_t resample_lds_floats(int up, int down, int J) {
 }
 
 // n_streams > 1: the same output range of n_streams streams in one launch (grid.y = stream), each stream's input
-// src_stride floats after the previous one's and its output dst_stride floats after; bit for bit the outputs of
+// src_stride samples (of T) after the previous one's and its output dst_stride floats after; bit for bit the outputs of
 // n_streams single launches (same staging, same fma chain per output). With hist_n > 0 the input is two parts:
 // stream frames [in_base - hist_n, in_base) from hist (hist_stride per stream), then [in_base, in_base + n) from src.
-void launch_resample(const float *src, int64_t in_base, int64_t n, int channels, int up, int down, int hl, int J,
-                     const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s, int n_streams,
-                     int64_t src_stride, int64_t dst_stride, const float *hist, int64_t hist_n, int64_t hist_stride) {
+template <typename T>
+static void launch_resample_t(const T *src, int64_t in_base, int64_t n, int channels, int up, int down, int hl, int J,
+                              const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s, int n_streams,
+                              int64_t src_stride, int64_t dst_stride, const T *hist, int64_t hist_n, int64_t hist_stride) {
     if (count <= 0 || n_streams <= 0) return;
-    const ResIn in{hist_n > 0 ? hist : src, in_base - hist_n, hist_n, hist_stride, src, in_base, n, src_stride};
+    const ResInT<T> in{hist_n > 0 ? hist : src, in_base - hist_n, hist_n, hist_stride, src, in_base, n, src_stride};
     if (use_phase(up, down, J)) {
         const int64_t per = (int64_t)up * kResR;
         const dim3 g((unsigned)((count + per - 1) / per), (unsigned)n_streams), b((unsigned)std::min(256, (up + 63) / 64 * 64));
         const size_t lds = (size_t)resample_lds_floats(up, down, J) * sizeof(float);
         if (channels == 2)
-            hipLaunchKernelGGL((k_resample_phase<true>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
+            hipLaunchKernelGGL((k_resample_phase<true, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
                                m_first + count, dst_stride);
         else
-            hipLaunchKernelGGL((k_resample_phase<false>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
+            hipLaunchKernelGGL((k_resample_phase<false, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
                                m_first + count, dst_stride);
         return;
     }
@@ -311,10 +355,10 @@ void launch_resample(const float *src, int64_t in_base, int64_t n, int channels,
         const dim3 g((unsigned)((count + kDecThreads * kDecR - 1) / (kDecThreads * kDecR)), (unsigned)n_streams);
         const size_t lds = (size_t)(dec_window<3, 61>() + 4) * sizeof(float);
         if (channels == 2)
-            hipLaunchKernelGGL((k_decimate<true, 3, 61>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
+            hipLaunchKernelGGL((k_decimate<true, 3, 61, T>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
                                m_end, dst_stride);
         else
-            hipLaunchKernelGGL((k_decimate<false, 3, 61>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
+            hipLaunchKernelGGL((k_decimate<false, 3, 61, T>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
                                m_end, dst_stride);
         return;
     }
@@ -323,13 +367,39 @@ void launch_resample(const float *src, int64_t in_base, int64_t n, int channels,
     const size_t lds = (size_t)resample_lds_floats(up, down, J) * sizeof(float);
     const int mode = up == 1 ? 2 : taps_in_lds(up, J) ? 1 : 0;
 #define AID_RS_LAUNCH(ST, MD) \
-    hipLaunchKernelGGL((k_resample<ST, MD>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first, m_end, dst_stride)
+    hipLaunchKernelGGL((k_resample<ST, MD, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first, m_end, dst_stride)
     if (channels == 2) {
         if (mode == 2) AID_RS_LAUNCH(true, 2); else if (mode == 1) AID_RS_LAUNCH(true, 1); else AID_RS_LAUNCH(true, 0);
     } else {
         if (mode == 2) AID_RS_LAUNCH(false, 2); else if (mode == 1) AID_RS_LAUNCH(false, 1); else AID_RS_LAUNCH(false, 0);
     }
 #undef AID_RS_LAUNCH
+}
+
+// src / hist: float samples, or int16 with s16 (strides then count int16)
+void launch_resample(const void *src, bool s16, int64_t in_base, int64_t n, int channels, int up, int down, int hl, int J,
+                     const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s, int n_streams,
+                     int64_t src_stride, int64_t dst_stride, const void *hist, int64_t hist_n, int64_t hist_stride) {
+    if (s16)
+        launch_resample_t(static_cast<const int16_t *>(src), in_base, n, channels, up, down, hl, J, taps, dst, m_first,
+                          count, s, n_streams, src_stride, dst_stride, static_cast<const int16_t *>(hist), hist_n,
+                          hist_stride);
+    else
+        launch_resample_t(static_cast<const float *>(src), in_base, n, channels, up, down, hl, J, taps, dst, m_first,
+                          count, s, n_streams, src_stride, dst_stride, static_cast<const float *>(hist), hist_n,
+                          hist_stride);
+}
+
+// n mono s16 samples -> float (aid_resample_s16 at equal rates, mono: the float sibling's copy)
+__global__ __launch_bounds__(256) void k_s16_to_f32(const int16_t *__restrict__ src, int64_t n, float *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = s16_val(src[i]);
+}
+
+void launch_s16_to_f32(const int16_t *src, int64_t n, float *dst, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, s, src, n,
+                       dst);
 }
 
 }  // namespace aid

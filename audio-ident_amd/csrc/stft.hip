@@ -93,22 +93,52 @@ __device__ __forceinline__ void pstore(float *p, float v) {
 // pairs are only 4-byte aligned: they are read through a 2-float vector type declared 4-byte aligned (the same
 // global_load_dwordx2; a float2 pointer would promise the compiler 8 bytes)
 typedef float aid_f2u __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ float2 pcm_ld(const aid_f2u &r) {
-    const aid_f2u v = __builtin_nontemporal_load(&r);
-    return make_float2(v.x, v.y);
-}
-#define AID_PCM(ref) pcm_ld(ref)
+// Integer PCM (FPSPEC 8): a lane's pair of s16 samples is one dword, and an s16 clip may start at any sample, so
+// the pair is only 2-byte aligned: the type says so and hipcc picks one dword load or two halfword loads
+typedef uint32_t aid_s2u __attribute__((aligned(2)));
+
+// The ring of one sample format: `pair` is what a lane loads per row, `slot` what the ring keeps of it, val() the
+// two samples as FPSPEC values, pin() an empty asm reading the slot's registers
+template <typename T>
+struct PcmRing;
+template <>
+struct PcmRing<float> {
+    typedef aid_f2u pair;
+    typedef float2 slot;
+    static __device__ __forceinline__ slot ld(const pair &r) {
+        const aid_f2u v = __builtin_nontemporal_load(&r);
+        return make_float2(v.x, v.y);
+    }
+    static __device__ __forceinline__ float2 val(slot s) { return s; }
+    static __device__ __forceinline__ void pin(slot s) { asm volatile("" ::"v"(s.x), "v"(s.y)); }
+};
+// s16: the ring keeps the packed pair (16 VGPRs instead of 32) and converts at the window multiply:
+// x = float(q) * 2^-15, both steps exact (FPSPEC 8), so the product with the window is the float path's one rounding
+template <>
+struct PcmRing<int16_t> {
+    typedef aid_s2u pair;
+    typedef uint32_t slot;
+    static __device__ __forceinline__ slot ld(const pair &r) { return __builtin_nontemporal_load(&r); }
+    static __device__ __forceinline__ float2 val(slot s) {
+        // the empty asm keeps the conversion at the multiply: hipcc otherwise converted the slots of the next
+        // frames early and held them as floats beside the ring (hop 512: 128 VGPRs and a 12-byte spill; 122 with it)
+        asm volatile("" : "+v"(s));
+        return make_float2((float)(int16_t)(s & 0xFFFFu) * 0x1p-15f, (float)((int32_t)s >> 16) * 0x1p-15f);
+    }
+    static __device__ __forceinline__ void pin(slot s) { asm volatile("" ::"v"(s)); }
+};
 
 __device__ __forceinline__ int e3q_slot(int k) { return 4 * (k & 255) + ((k >> 8) ^ (2 * ((k >> 3) & 1))); }
 
-template <bool LOGMAG, int ROWS>
-__global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_stft_power(const float *__restrict__ pcm,
+template <bool LOGMAG, int ROWS, typename T = float>
+__global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_stft_power(const T *__restrict__ pcm,
                                                                 const ClipDesc *__restrict__ clips, int n_clips,
                                                                 int64_t f0, int64_t total, int64_t n_waves,
                                                                 const Tables *__restrict__ tab, float *__restrict__ out,
                                                                 uint64_t *__restrict__ hot, float thr, int keep) {
     constexpr int PERIOD = 16 / ROWS;  // frames per full ring rotation
-    constexpr int HOP2 = 64 * ROWS;    // hop in float2 units
+    constexpr int HOP2 = 64 * ROWS;    // hop in sample pairs
+    typedef PcmRing<T> Ring;
     __shared__ __attribute__((aligned(16))) float2 lds[kStftWaves][kStftLdsPerWave];  // E1 regions, then E3
     // tables as float4 pairs [h][lane], one ds_read_b128 per pair (hipcc would otherwise merge the
     // stride-512-B float2 reads into ds_read2st64_b64, which costs the LDS twice the cycles):
@@ -179,19 +209,20 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     }
     const int64_t t0 = f - clips[lo].frame_base;
     const int nfr = (int)min(f_end - f, clips[lo].frames - t0);
-    const aid_f2u *src = reinterpret_cast<const aid_f2u *>(pcm + clips[lo].pcm_off) + t0 * HOP2 + e1_perm(lane);
+    const typename Ring::pair *src =
+        reinterpret_cast<const typename Ring::pair *>(pcm + clips[lo].pcm_off) + t0 * HOP2 + e1_perm(lane);
     float *dst = out + (clips[lo].frame_base - f0 + t0) * kBins;
     uint64_t *dhot = LOGMAG ? nullptr : hot + clips[lo].frame_base + t0;
 
-    float2 ring[16];
+    typename Ring::slot ring[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) ring[r] = AID_PCM(src[64 * r]);
+    for (int r = 0; r < 16; ++r) ring[r] = Ring::ld(src[64 * r]);
     // the segment's first frame needs the whole ring anyway: wait for it here, so the frame loop's
     // header does not inherit this path's pending loads (hipcc's wait at the header, merged over both
     // edges, was vmcnt(1): every 4 frames the wave also waited for the previous frame's 17 stores)
     // (an empty asm reading every ring register: hipcc must complete the loads before it)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(ring[r].x), "v"(ring[r].y));
+    for (int r = 0; r < 16; ++r) Ring::pin(ring[r]);
 
     for (int f0 = 0; f0 < nfr; f0 += PERIOD) {
 #pragma unroll
@@ -208,7 +239,7 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                 for (int h = 0; h < 8; ++h) {
                     const float4 w = wpf[h];
-                    const float2 x0 = ring[(2 * h + ROWS * p) & 15], x1 = ring[(2 * h + 1 + ROWS * p) & 15];
+                    const float2 x0 = Ring::val(ring[(2 * h + ROWS * p) & 15]), x1 = Ring::val(ring[(2 * h + 1 + ROWS * p) & 15]);
                     v[2 * h] = make_float2(x0.x * w.x, x0.y * w.y);
                     v[2 * h + 1] = make_float2(x1.x * w.z, x1.y * w.w);
                 }
@@ -218,7 +249,7 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                     const int fn = min(f + 1, nfr - 1);
 #pragma unroll
                     for (int j = 0; j < ROWS; ++j)
-                        ring[(ROWS * p + j) & 15] = AID_PCM(src[(int64_t)fn * HOP2 + 64 * (16 - ROWS + j)]);
+                        ring[(ROWS * p + j) & 15] = Ring::ld(src[(int64_t)fn * HOP2 + 64 * (16 - ROWS + j)]);
                 }
                 // stage A: lane = n2
                 dft16(v, t16);
@@ -453,22 +484,23 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     }
 }
 
-template <bool LOGMAG>
-static void launch_rows(int rows, dim3 g, dim3 b, hipStream_t s, const float *pcm, const ClipDesc *clips, int n_clips,
+template <bool LOGMAG, typename T>
+static void launch_rows(int rows, dim3 g, dim3 b, hipStream_t s, const T *pcm, const ClipDesc *clips, int n_clips,
                         int64_t f0, int64_t total, int64_t n_waves, const Tables *tab, float *out, uint64_t *hot, float thr,
                         int keep) {
     switch (rows) {
-        case 1: timed_launch((k_stft_power<LOGMAG, 1>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 2: timed_launch((k_stft_power<LOGMAG, 2>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 4: timed_launch((k_stft_power<LOGMAG, 4>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 8: timed_launch((k_stft_power<LOGMAG, 8>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        default: timed_launch((k_stft_power<LOGMAG, 16>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        case 1: timed_launch((k_stft_power<LOGMAG, 1, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        case 2: timed_launch((k_stft_power<LOGMAG, 2, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        case 4: timed_launch((k_stft_power<LOGMAG, 4, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        case 8: timed_launch((k_stft_power<LOGMAG, 8, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        default: timed_launch((k_stft_power<LOGMAG, 16, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
     }
 }
 
 // total_frames = sum of the clips' frames, the first at absolute frame f0 (out = its power row),
-// total_strips = sum of ceil(F / kStftStrip) (strip mode), slots = resident K1 waves on the device (CUs x kStftWaves)
-void launch_stft_power(const float *pcm, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
+// total_strips = sum of ceil(F / kStftStrip) (strip mode), slots = resident K1 waves on the device (CUs x kStftWaves).
+// s16: pcm is int16 samples (ClipDesc::pcm_off counts samples either way); the log-magnitude rows are float-only
+void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
                        int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
                        uint64_t *hot, float thr, bool keep_power, hipStream_t s) {
     if (total_frames <= 0) return;
@@ -479,9 +511,13 @@ void launch_stft_power(const float *pcm, const ClipDesc *clips, int n_clips, int
         1, total_frames >= slots * kStftStrip ? slots : std::min<int64_t>(slots, total_frames / kK1MinFrames));
     const int64_t total = total_frames;
     const dim3 g((unsigned)((n_waves + kStftWaves - 1) / kStftWaves)), b(kStftWaves * 64);
-    if (logmag) launch_rows<true>(hop / 128, g, b, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, nullptr, thr, 1);
+    const float *f32 = static_cast<const float *>(pcm);
+    if (logmag) launch_rows<true>(hop / 128, g, b, s, f32, clips, n_clips, f0, total, n_waves, tab, out, nullptr, thr, 1);
+    else if (s16)
+        launch_rows<false>(hop / 128, g, b, s, static_cast<const int16_t *>(pcm), clips, n_clips, f0, total, n_waves, tab,
+                           out, hot, 4.0f * thr, keep_power ? 1 : 0);
     else  // the power plane holds 4P (see the real split): hot blocks are those with 4P > 4 thr
-        launch_rows<false>(hop / 128, g, b, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, 4.0f * thr,
+        launch_rows<false>(hop / 128, g, b, s, f32, clips, n_clips, f0, total, n_waves, tab, out, hot, 4.0f * thr,
                            keep_power ? 1 : 0);
 }
 

@@ -9,7 +9,8 @@ image), converted to f32 as ffmpeg's f32le output would be (sample / 32768, exac
 
     python bench_cpu_wav.py [--seconds 10] [--repeat 20] [--gpu]
 
---gpu also fingerprints the decoded clip on the MI355X and checks the hashes are identical.
+--gpu also fingerprints the clip on the MI355X and checks the hashes are identical: the engine gets the WAV's own
+int16 samples (fmt="s16", spec/FPSPEC.md 8), not the widened floats the CPU path reads.
 """
 
 from __future__ import annotations
@@ -65,7 +66,8 @@ def main() -> int:
         from aidfp.engine import Engine
 
         with Engine(sr) as eng:
-            got = eng.extract_host([x])[0]
+            got = eng.extract_host([data], fmt="s16")[0]  # the WAV's int16 samples as they are
+        out["gpu_pcm"] = "s16"
         out["gpu_hashes_identical"] = bool(np.array_equal(got, recs))
     print(json.dumps(out), flush=True)
     return 0

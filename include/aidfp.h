@@ -127,6 +127,17 @@ int64_t aid_hash_capacity(const aid_engine *e, int64_t n_samples);
  */
 int aid_extract(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t pcm_location,
                 void *stream);
+/*
+ * Integer PCM (spec/FPSPEC.md 8): every PCM entry point has an _s16 twin that takes native-endian (little-endian)
+ * int16 samples where its sibling takes floats. A sample's value is x = float(q) * 2^-15, exact in binary32 and
+ * equal to q / 32768, so an _s16 call computes bit for bit what its float sibling computes on the widened samples;
+ * the conversion happens in the kernels' loads (K1's ring, K6's staging), and a host batch is staged by a copy of
+ * half the bytes. Offsets, starts, ends and strides count samples (frames for stereo) exactly as in the sibling;
+ * an s16 clip may start at any sample (2-byte alignment), a stereo s16 frame is 4-byte aligned. WAV data, capture
+ * devices and the reference's decode test vector are all s16: no host widening is needed.
+ */
+int aid_extract_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t pcm_location,
+                    void *stream);
 
 /* Block until the last extraction finished. */
 int aid_sync(aid_engine *e);
@@ -235,6 +246,10 @@ int aid_index_csr_export(aid_engine *e, uint32_t *offsets, int64_t n_offsets, ui
 int64_t aid_resample_len(int64_t n, int32_t sr_in, int32_t sr_out);
 int aid_resample(aid_engine *e, const float *src, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out,
                  float *dst, int64_t cap, int64_t *n_out, void *stream);
+/* src = n frames of `channels` int16 (stereo: interleaved, downmixed as (xL + xR) * 0.5f on the converted values);
+   dst is float as above. */
+int aid_resample_s16(aid_engine *e, const int16_t *src, int64_t n, int32_t channels, int32_t sr_in, int32_t sr_out,
+                     float *dst, int64_t cap, int64_t *n_out, void *stream);
 /* Streaming form: src[0] is stream sample in_base (samples outside [in_base, in_base+n) read as 0);
  * computes stream outputs [m_first, m_first+count) into dst[0..count). Output m needs inputs up to
  * floor((m*down + hl)/up) and J-1 before it, so a caller that keeps that history gets exactly the
@@ -257,6 +272,12 @@ int aid_resample_batch_split(aid_engine *e, const float *hist, int64_t hist_stri
                              int64_t src_stride, int32_t n_streams, int64_t in_base, int64_t n, int32_t channels,
                              int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count, float *dst,
                              int64_t dst_stride, void *stream);
+/* The same over int16 input: hist and src are both s16, hist_stride and src_stride count int16 (dst_stride floats);
+ * hist_n = 0 is the batch form, n_streams = 1 the range form (a 256-stream 2.5 s push is 123 MB of s16 stereo). */
+int aid_resample_batch_split_s16(aid_engine *e, const int16_t *hist, int64_t hist_stride, int64_t hist_n,
+                                 const int16_t *src, int64_t src_stride, int32_t n_streams, int64_t in_base, int64_t n,
+                                 int32_t channels, int32_t sr_in, int32_t sr_out, int64_t m_first, int64_t count,
+                                 float *dst, int64_t dst_stride, void *stream);
 /* (up, down, hl, J) of a rate pair (FPSPEC 8); returns 0 on bad rates */
 int aid_resample_plan(int32_t sr_in, int32_t sr_out, int32_t *up, int32_t *down, int32_t *hl, int32_t *J);
 
@@ -329,11 +350,15 @@ int aid_query_extracted(aid_engine *e, aid_match_row *rows, int32_t *nrows);
    fingerprint.py:185-193). Synchronous. */
 int aid_query_pcm(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t pcm_location,
                   aid_match_row *rows, int32_t *nrows, void *stream);
+int aid_query_pcm_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t pcm_location,
+                      aid_match_row *rows, int32_t *nrows, void *stream);
 /* aid_query_pcm over windows of DEVICE PCM given as [starts[c], ends[c]) sample ranges, which may overlap
  * (50 %-overlap stream windows, sub-windows of one clip): K1-K3 read them in place, then K5, in one critical
  * section. Rows as aid_query. Replaces one `olaf_c query` per window (fingerprint.py:185-193). */
 int aid_query_windows(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends, int32_t n_windows,
                       aid_match_row *rows, int32_t *nrows, void *stream);
+int aid_query_windows_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts, const int64_t *ends,
+                          int32_t n_windows, aid_match_row *rows, int32_t *nrows, void *stream);
 /* The same query in two halves (a caller overlaps its next batch's host work with this batch's
  * kernels). _submit enqueues the extraction, K5 and the result copies on `stream` and returns a ticket at once;
  * _collect waits for that ticket's work, answers any query the fast match path handed back, writes the rows exactly
@@ -343,12 +368,17 @@ int aid_query_windows(aid_engine *e, const float *pcm, const int64_t *starts, co
 typedef struct aid_query_ticket aid_query_ticket;
 int aid_query_windows_submit(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends,
                              int32_t n_windows, void *stream, aid_query_ticket **ticket);
+/* (an _s16 ticket is collected with aid_query_windows_collect like any other) */
+int aid_query_windows_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts, const int64_t *ends,
+                                 int32_t n_windows, void *stream, aid_query_ticket **ticket);
 int aid_query_windows_collect(aid_engine *e, aid_query_ticket *ticket, aid_match_row *rows, int32_t *nrows);
 /* aid_query_pcm in the same two halves (the query coalescer's pipelined batches, replacing the per-request
  * `olaf_c query` processes of fingerprint.py:185-193): HOST PCM is copied to the device in stream order, so the
  * caller keeps it unchanged until it has collected the ticket (with aid_query_windows_collect). */
 int aid_query_pcm_submit(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips,
                          int32_t pcm_location, void *stream, aid_query_ticket **ticket);
+int aid_query_pcm_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
+                             int32_t pcm_location, void *stream, aid_query_ticket **ticket);
 
 /* Batched exact lane: replaces app/search/exact.py run_exact_lane's
    sub-window fan-out, the olaf_query calls and the consensus (exact.py:70-124, :132-353) for a
@@ -366,6 +396,9 @@ typedef struct aid_exact_row {
 } aid_exact_row;
 int aid_exact_lane(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t pcm_location,
                    int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream);
+/* s16 clips: the sub-windows are read in place as above (under AID_FORCE_LANE_GATHER the gather converts them) */
+int aid_exact_lane_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
+                       int32_t pcm_location, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream);
 /* The lane's window plan for a clip of n samples (host only, no device): returns the number of
    windows (3 for clips <= 5 s, mode 1; else 1 whole-clip window, mode 0) with sample bounds
    lo[w], len[w] (len 0 = no query, as the reference's empty piece, exact.py:150-160, :374-399). */
