@@ -49,7 +49,8 @@ class AidConfig(ctypes.Structure):
         ("min_match", ctypes.c_int32),
         ("max_results", ctypes.c_int32),
         ("flags", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 9),
+        ("peak_rel", ctypes.c_float),  # FPSPEC 5.1: 0 = off, else thr_c = max(peak_threshold, peak_rel * Pmax_c)
+        ("reserved", ctypes.c_int32 * 8),
     ]
 
 
@@ -97,6 +98,7 @@ SIGNATURES = [
     ("aid_result_device", ctypes.c_int, [P, P, P, P, P]),
     ("aid_result_power", ctypes.c_int, [P, I32, P, I64]),
     ("aid_result_peakmask", ctypes.c_int, [P, I32, P, I64]),
+    ("aid_result_thresholds", ctypes.c_int, [P, P]),
     ("aid_spectrogram", ctypes.c_int, [P, P, I64, P, I64]),
     ("aid_synth", ctypes.c_int, [P, P, P, P, I32, I64, I32, ctypes.c_uint32, P]),
     ("aid_synth_band", ctypes.c_int, [P, P, P, P, I32, I64, I32, ctypes.c_uint32, I32, P]),

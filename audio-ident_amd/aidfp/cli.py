@@ -9,7 +9,8 @@ makes (audio-ident-service/app/audio/fingerprint.py:117-125, 185-193, 239-246):
 raw 16 kHz mono f32le input, exit code 0 on success, query results on stdout as
 `match_count, q_start, q_stop, ref_path, ref_id, ref_start, ref_stop` lines.
 Point settings.olaf_bin_path at the `aidfp_olaf_c` wrapper to
-swap engines without editing the service.
+swap engines without editing the service. Env AIDFP_PEAK_TOP_DB (and AIDFP_PEAK_FLOOR) select the
+gain-invariant peak rule (spec/FPSPEC.md 5.1) for every subcommand: store and query must agree on it.
 """
 
 from __future__ import annotations

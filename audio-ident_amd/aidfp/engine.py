@@ -25,6 +25,18 @@ N_FFT = 2048
 BINS = 1024
 
 
+def top_db_to_rel(top_db: float) -> float:
+    """peak_rel of "top_db below the loudest bin" (FPSPEC 5.1): float32(10 ** (-top_db / 10)), computed in binary64
+    and rounded once. top_db must be > 0 (and small enough for the result to stay >= 2^-60)."""
+    top_db = float(top_db)
+    if not top_db > 0.0:  # also NaN
+        raise ValueError(f"top_db must be > 0, got {top_db!r}")
+    r = float(np.float32(10.0 ** (-top_db / 10.0)))
+    if not 2.0 ** -60 <= r < 1.0:
+        raise ValueError(f"top_db = {top_db!r} gives peak_rel = {r!r}, outside [2^-60, 1)")
+    return r
+
+
 def _p(a: np.ndarray) -> ctypes.c_void_p:
     return ctypes.c_void_p(a.ctypes.data)
 
@@ -221,7 +233,14 @@ def _host_concat(arrs: list[np.ndarray], total: int, slot: "_PinnedSlot | None" 
 
 class Engine:
     def __init__(self, sample_rate: int, hop: int = 0, peak_threshold: float = 0.0, device: int = -1,
-                 min_match: int = 0, max_results: int = 0, keep_power: bool = False):
+                 min_match: int = 0, max_results: int = 0, keep_power: bool = False, peak_rel: float = 0.0,
+                 top_db: float | None = None):
+        """peak_rel / top_db (FPSPEC 5.1, one of them at most): the gain-invariant peak rule. Each clip's threshold
+        is max(peak_threshold, peak_rel * the clip's largest power); peak_threshold becomes the absolute floor."""
+        if top_db is not None:
+            if peak_rel:
+                raise ValueError("pass peak_rel or top_db, not both")
+            peak_rel = top_db_to_rel(top_db)
         lib = L.load()
         cfg = AidConfig()
         check(lib.aid_config_default(int(sample_rate), ctypes.byref(cfg)))
@@ -229,6 +248,7 @@ class Engine:
             cfg.hop = hop
         if peak_threshold:
             cfg.peak_threshold = peak_threshold
+        cfg.peak_rel = peak_rel  # validated by aid_engine_create
         cfg.device = device
         if min_match:
             cfg.min_match = min_match
@@ -249,6 +269,7 @@ class Engine:
         self.sample_rate = out.sample_rate
         self.hop = out.hop
         self.peak_threshold = out.peak_threshold
+        self.peak_rel = out.peak_rel
         self.device = out.device
         self.min_match = out.min_match
         self.max_results = out.max_results
@@ -333,6 +354,15 @@ class Engine:
             check(rc)
         out = np.zeros(max(1, n.value), dtype=np.uint64)
         check(self._lib.aid_result_hashes(self._h, clip, _p(out), n.value, ctypes.byref(n)))
+        return out[: n.value]
+
+    def thresholds(self) -> np.ndarray:
+        """Effective peak threshold thr_c of every clip of the last extraction (float32; FPSPEC 5.1). With
+        peak_rel = 0 it is peak_threshold for every clip."""
+        n = ctypes.c_int32()
+        check(self._lib.aid_result_device(self._h, None, None, None, ctypes.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=np.float32)
+        check(self._lib.aid_result_thresholds(self._h, _p(out)))
         return out[: n.value]
 
     def device_view(self):

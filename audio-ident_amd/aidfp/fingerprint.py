@@ -113,6 +113,27 @@ def resolve_pcm_format(name: str | None = None) -> str:
     return fmt
 
 
+def resolve_peak_rule(top_db: float | None = None, floor: float | None = None) -> dict:
+    """The engine's peak rule as Engine keyword arguments (FPSPEC 5.1). top_db: the argument, else env
+    AIDFP_PEAK_TOP_DB, else off (the absolute threshold, FPSPEC 5). floor: the argument, else env AIDFP_PEAK_FLOOR,
+    else the engine's default peak_threshold (4.0), which in relative mode is the absolute floor: quiet queries
+    need it well below their own peaks (e.g. 2^-20). An index must be queried under the rule it was built with."""
+    kw: dict = {}
+    if top_db is None and os.environ.get("AIDFP_PEAK_TOP_DB"):
+        top_db = float(os.environ["AIDFP_PEAK_TOP_DB"])
+    if floor is None and os.environ.get("AIDFP_PEAK_FLOOR"):
+        floor = float(os.environ["AIDFP_PEAK_FLOOR"])
+    if top_db is not None:
+        from .engine import top_db_to_rel
+
+        kw["peak_rel"] = top_db_to_rel(top_db)  # raises on top_db <= 0
+    if floor is not None:
+        if not floor > 0.0:
+            raise ValueError(f"peak floor must be > 0, got {floor!r}")
+        kw["peak_threshold"] = float(floor)
+    return kw
+
+
 class _Answered:
     """A coalesced batch answered at submit time (its engine submit failed and the synchronous path ran)."""
 
@@ -153,7 +174,10 @@ class FingerprintService:
     def __init__(self, db_dir: Path | None = None, device: int = -1, checkpoint_min_bytes: int = 64 << 20,
                  coalesce_window_s: float | None = None, max_batch: int = 256, max_batch_bytes: int = 64 << 20,
                  coalesce_workers: int = 1, pipeline: bool = True, split_min: int = 16, split_parts: int = 2,
-                 pcm_format: str | None = None):
+                 pcm_format: str | None = None, peak_top_db: float | None = None, peak_floor: float | None = None):
+        # the peak rule of this service's engine (resolve_peak_rule: arguments, else env AIDFP_PEAK_TOP_DB /
+        # AIDFP_PEAK_FLOOR, else the FPSPEC 5 default); the index on disk does not record it
+        self._peak_kw = resolve_peak_rule(peak_top_db, peak_floor)
         self.db_dir = Path(db_dir) if db_dir is not None else db_path()
         # one format per service (default: env AIDFP_PCM_FORMAT, else "f32"): the coalescer merges concurrent
         # requests into one engine call, so formats cannot mix inside a service. The index is the same either way
@@ -205,7 +229,7 @@ class FingerprintService:
             from .store import OP_STORE, IndexStore, StoreCorrupt
 
             try:
-                eng = Engine(SAMPLE_RATE, device=self.device)
+                eng = Engine(SAMPLE_RATE, device=self.device, **self._peak_kw)
             except (EngineUnavailable, EngineError, OSError) as exc:
                 raise OlafError(f"fingerprint engine binary not found or unusable (libaidfp.so): {exc}") from exc
             store = IndexStore(self.db_dir, self.checkpoint_min_bytes)

@@ -25,10 +25,11 @@
 namespace aid {
 void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
                        int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
-                       uint64_t *hot, float thr, bool keep_power, hipStream_t s);
+                       uint64_t *hot, float thr, bool keep_power, uint32_t *qmax, hipStream_t s);
 int peak_pick_blocks_per_cu();
 void launch_peak_pick(const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
-                      int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt, hipStream_t s);
+                      int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
+                      const uint32_t *clip_qmax, float rel, hipStream_t s);
 void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
                       int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
                       uint64_t *k2_cold_host, uint32_t k2_waves, bool one_chunk_each, hipStream_t s);
@@ -186,6 +187,9 @@ struct aid_engine {
     DevBuf<float> power;
     DevBuf<uint64_t> mask;
     DevBuf<uint64_t> hotw;  // K1 -> K2: per power row, bit hot_bit(c) = 16-bin chunk c has a value > thr
+    // FPSPEC 5.1 (cfg.peak_rel > 0): per clip of the call, the bit pattern of max Q over its plane. Zeroed on the
+    // call's stream before the first K1, raised by K1's atomics, read by K2 and aid_result_thresholds
+    DevBuf<uint32_t> clip_qmax;
     DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64), summed and reset by K3
     uint64_t *h_cold = nullptr;      // pinned, host-mapped: K3 stores (cold waves | waves << 32) of the last K2 here
     uint64_t *h_cold_dev = nullptr;  // its device address
@@ -413,6 +417,10 @@ int aid_engine_create(const aid_config *cfg, aid_engine **out) {
     // any Q of a candidate (Q > 4 thr) is normal, so Q-order and P-order decide every comparison alike
     if (!(c.peak_threshold >= 0x1p-124f) || c.peak_threshold > 0x1p100f)
         return fail(AID_ERR_INVALID, "peak_threshold must be in [2^-124, 2^100]");
+    // FPSPEC 5.1: 0 = off; else the clip's threshold is max(peak_threshold, peak_rel * max P). Below 1 (at 1 and
+    // above no bin can exceed the threshold); from 2^-60 (the product with any P that matters stays normal)
+    if (c.peak_rel != 0.0f && !(c.peak_rel >= 0x1p-60f && c.peak_rel < 1.0f))
+        return fail(AID_ERR_INVALID, "peak_rel must be 0 or in [2^-60, 1)");
     if (c.min_match <= 0) c.min_match = 10;
     if (c.max_results <= 0) c.max_results = 50;
     if (c.flags & ~AID_FLAG_KEEP_POWER) return fail(AID_ERR_INVALID, "unknown aid_config.flags bits");
@@ -492,6 +500,7 @@ void aid_engine_destroy(aid_engine *e) {
     e->pcm_stage.release();
     e->power.release();
     e->k2_cold.release();
+    e->clip_qmax.release();
     if (e->h_cold) (void)hipHostFree(e->h_cold);
     e->mask.release();
     e->desc.release();
@@ -796,6 +805,13 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
     HIP_TRY(e->power.reserve((size_t)std::max<int64_t>(1, *std::max_element(gframes.begin(), gframes.end())) * kBins));
     HIP_TRY(e->mask.reserve((size_t)frames * kMaskWords));
     HIP_TRY(e->hotw.reserve((size_t)frames + 1));
+    // relative mode: the clips' maxima start at +0 on this call's stream, ahead of the first group's K1 (ordered
+    // against earlier calls on other streams as hotw and mask are, by the stream wait above)
+    const bool rel = e->cfg.peak_rel > 0.0f;
+    if (rel) {
+        HIP_TRY(e->clip_qmax.reserve((size_t)n_clips + 1));
+        if (n_clips > 0) HIP_TRY(hipMemsetAsync(e->clip_qmax.p, 0, sizeof(uint32_t) * (size_t)n_clips, s));
+    }
     if (!e->k2_cold.p) {
         HIP_TRY(e->k2_cold.reserve(64));
         HIP_TRY(hipMemsetAsync(e->k2_cold.p, 0, 64 * sizeof(uint32_t), s));
@@ -853,7 +869,7 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
                 ProfScope ps(e, AID_K_STFT, s, true);
                 launch_stft_power(dpcm, fmt == kS16, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab,
                                   e->power.p, false, e->hotw.p, e->cfg.peak_threshold,
-                                  (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0, s);
+                                  (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0, rel ? e->clip_qmax.p + ca : nullptr, s);
             }
             if (loc == AID_PCM_HOST && g == n_groups - 1) {
                 if (!e->stage_ev) HIP_TRY(hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming));
@@ -864,7 +880,8 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
             {
                 ProfScope ps(e, AID_K_PEAKS, s, true);
                 launch_peak_pick(e->power.p, e->desc.p + ca, ng, gfirst[g], gstrips[g], glen[g], e->cfg.peak_threshold,
-                                 e->hotw.p, e->mask.p, e->k2_cold.p, s);
+                                 e->hotw.p, e->mask.p, e->k2_cold.p, rel ? e->clip_qmax.p + ca : nullptr,
+                                 e->cfg.peak_rel, s);
             }
         }
         if (multi_chunk) {  // some clip spans several K3 chunks: their bases need the COUNT pass
@@ -946,6 +963,28 @@ int aid_result_power(aid_engine *e, int32_t clip, float *out, int64_t cap) {
     return AID_OK;
 }
 
+int aid_result_thresholds(aid_engine *e, float *out) {
+    if (!e || (!out && e->n_clips > 0)) return fail(AID_ERR_INVALID, "null argument");
+    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
+    if (int rc = aid_sync(e)) return rc;
+    const float thr = e->cfg.peak_threshold, r = e->cfg.peak_rel;
+    if (!(r > 0.0f) || e->n_clips == 0) {
+        for (int c = 0; c < e->n_clips; ++c) out[c] = thr;
+        return AID_OK;
+    }
+    std::vector<uint32_t> q((size_t)e->n_clips);
+    HIP_TRY(hipMemcpy(q.data(), e->clip_qmax.p, sizeof(uint32_t) * q.size(), hipMemcpyDeviceToHost));
+    for (int c = 0; c < e->n_clips; ++c) {
+        // FPSPEC 5.1 in the spec's own terms: Pmax = Qmax * 0.25f (the readout scaling of aid_result_power; the
+        // maximum commutes with it), one binary32 multiply by r, then the maximum with the floor
+        float qm;
+        std::memcpy(&qm, &q[c], sizeof(qm));
+        const float t = r * (qm * 0.25f);
+        out[c] = t > thr ? t : thr;
+    }
+    return AID_OK;
+}
+
 int aid_result_peakmask(aid_engine *e, int32_t clip, uint64_t *out, int64_t cap) {
     if (!e) return fail(AID_ERR_INVALID, "null engine");
     if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
@@ -981,7 +1020,7 @@ int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int6
     if (he == hipSuccess) he = hipMemcpy(d_desc, &d, sizeof(ClipDesc), hipMemcpyHostToDevice);
     if (he == hipSuccess) {
         launch_stft_power(d_pcm, false, d_desc, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop, e->d_tab,
-                          d_out, true, nullptr, e->cfg.peak_threshold, true, s);
+                          d_out, true, nullptr, e->cfg.peak_threshold, true, nullptr, s);
         he = hipGetLastError();
     }
     if (he == hipSuccess) he = hipStreamSynchronize(s);

@@ -72,7 +72,8 @@ __global__ __launch_bounds__(256, 4) void k_peak_pick(
                                                   const float *__restrict__ power, const ClipDesc *__restrict__ clips,
                                                   int n_clips, int64_t f0, int64_t total_strips, int strip_len, float thr,
                                                   const uint64_t *__restrict__ hot, uint64_t *__restrict__ mask,
-                                                  uint32_t *__restrict__ cold_cnt) {
+                                                  uint32_t *__restrict__ cold_cnt,
+                                                  const uint32_t *__restrict__ clip_qmax, float rel) {
     __shared__ __attribute__((aligned(16))) int rows[kRowsPerStep][kBins + 32];  // keys, 16 pads each side
     __shared__ __attribute__((aligned(16))) int bms[kRowsPerStep][256 + 8];  // block maxima, 4 pads each side
     // wave = the 256-bin quarter of the row this wave owns, rotated by the workgroup index: the
@@ -109,7 +110,11 @@ __global__ __launch_bounds__(256, 4) void k_peak_pick(
     const float *P = power + (fb - f0) * kBins;  // the plane holds rows from absolute frame f0 on
     uint64_t *M = mask + fb * kMaskWords + 4 * wave + lane;  // lanes 0..3 store ballot words
     // K1's plane holds Q = 4P (stft.hip, real split): compare against 4 thr (exact: thr <= 2^100)
-    const int kthr = __float_as_int(4.0f * thr);            // thr > 0 (engine config check)
+    int kthr = __float_as_int(4.0f * thr);                  // thr > 0 (engine config check)
+    // FPSPEC 5.1 (clip_qmax set): 4 thr_c = max(4 thr, rel * Qmax_c), Qmax_c = K1's maximum over the clip's whole
+    // plane (complete: a clip never spans a K1 -> K2 group). One uniform load per workgroup. Qmax_c is >= +0 and
+    // never NaN, so is the product, and both order like their keys; +inf gives key kInf: no candidate passes
+    if (clip_qmax) kthr = max(kthr, __float_as_int(rel * __uint_as_float(clip_qmax[lo])));
 
     if (tid < 16) {
 #pragma unroll
@@ -388,12 +393,14 @@ int k2_stamps_read(unsigned long long *out, bool reset) {
 #endif
 
 // power holds the rows from absolute frame f0 on (a group of the call's clips, extract_locked); the clips' strip_base
-// count from 0 within the group
+// count from 0 within the group. clip_qmax (FPSPEC 5.1): null = the absolute threshold thr alone; else the group's
+// words of K1's per-clip max Q, and every clip's threshold is max(thr, rel * its max P)
 void launch_peak_pick(const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
-                      int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt, hipStream_t s) {
+                      int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
+                      const uint32_t *clip_qmax, float rel, hipStream_t s) {
     if (total_strips <= 0) return;
     timed_launch(k_peak_pick, dim3((unsigned)total_strips), dim3(256), 0, s, power, clips, n_clips, f0, total_strips,
-                 strip_len, thr, hot, mask, cold_cnt);
+                 strip_len, thr, hot, mask, cold_cnt, clip_qmax, rel);
 }
 
 // resident K2 workgroups per CU (registers / LDS), for sizing strips to one round

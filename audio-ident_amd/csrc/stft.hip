@@ -26,6 +26,8 @@
 // (commit c236449, the AID_K1_* switches).
 #include "aidfp_device.h"
 
+#include <type_traits>
+
 // The add-TID writes below set M0 inside their asm and name it as clobbered; clang warns that M0 is a reserved
 // register whose value it will not preserve across the asm. Nothing else in this kernel may use M0:
 // tests/test_isa_m0.py compiles this file and fails on any M0 access outside these asm blocks. The warning
@@ -130,12 +132,16 @@ struct PcmRing<int16_t> {
 
 __device__ __forceinline__ int e3q_slot(int k) { return 4 * (k & 255) + ((k >> 8) ^ (2 * ((k >> 3) & 1))); }
 
-template <bool LOGMAG, int ROWS, typename T = float>
+// QMAX (FPSPEC 5.1, the per-clip relative threshold): the wave also folds every Q it computes into a running
+// maximum and publishes it per clip segment with one atomic on qmax[clip]. A template parameter, as LOGMAG: the
+// default instantiation carries none of it (K1 is VALU-bound)
+template <bool LOGMAG, int ROWS, typename T = float, bool QMAX = false>
 __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_stft_power(const T *__restrict__ pcm,
                                                                 const ClipDesc *__restrict__ clips, int n_clips,
                                                                 int64_t f0, int64_t total, int64_t n_waves,
                                                                 const Tables *__restrict__ tab, float *__restrict__ out,
-                                                                uint64_t *__restrict__ hot, float thr, int keep) {
+                                                                uint64_t *__restrict__ hot, float thr, int keep,
+                                                                uint32_t *__restrict__ qmax) {
     constexpr int PERIOD = 16 / ROWS;  // frames per full ring rotation
     constexpr int HOP2 = 64 * ROWS;    // hop in sample pairs
     typedef PcmRing<T> Ring;
@@ -214,6 +220,10 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     float *dst = out + (clips[lo].frame_base - f0 + t0) * kBins;
     uint64_t *dhot = LOGMAG ? nullptr : hot + clips[lo].frame_base + t0;
 
+    // QMAX: the lane's maximum of the segment's Q values. Q is >= +0 or a quiet NaN (a fma of squares), the
+    // maximum starts at +0 and is never NaN, and v_max_f32 returns its non-NaN operand: a NaN never raises it, +inf
+    // does (the same rule as K2's pkey). asm, because hipcc puts a canonicalising v_max x, x, x before each fmaxf
+    float qrun = 0.f;
     typename Ring::slot ring[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) ring[r] = Ring::ld(src[64 * r]);
@@ -418,6 +428,14 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                         const float p512 = __builtin_fmaf(xr, xr, xi * xi);
                         pstore(drow + 512, p512);
                         hotw |= p512 > thr ? 1ull << 63 : 0ull;  // chunk 32
+                        if constexpr (QMAX) asm("v_max_f32 %0, %0, %1" : "+v"(qrun) : "v"(p512));
+                    }
+                    if constexpr (QMAX) {  // the 16 registers the wave already holds (lane 0's pm[0] is 0)
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) {
+                            asm("v_max_f32 %0, %0, %1" : "+v"(qrun) : "v"(po[i]));
+                            asm("v_max_f32 %0, %0, %1" : "+v"(qrun) : "v"(pm[i]));
+                        }
                     }
                     dhot[f] = hotw;
                     // K2 reads only hot chunks (a value <= thr can neither be a peak nor suppress one, FPSPEC
@@ -480,29 +498,39 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
             }
         }
     }
+    if constexpr (QMAX) {
+        // the segment's maximum across the wave, then one vector atomic on the clip's word: non-negative
+        // non-NaN values order like their bit patterns, and a maximum does not depend on the order of its
+        // operands, so the clip's word is deterministic whatever the waves' timing
+        uint32_t qk = __float_as_uint(qrun);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) qk = max(qk, (uint32_t)__shfl_xor((int)qk, o));
+        if (lane == 0) atomicMax(qmax + lo, qk);
+    }
     f += nfr;
     }
 }
 
-template <bool LOGMAG, typename T>
+template <bool LOGMAG, bool QMAX, typename T>
 static void launch_rows(int rows, dim3 g, dim3 b, hipStream_t s, const T *pcm, const ClipDesc *clips, int n_clips,
                         int64_t f0, int64_t total, int64_t n_waves, const Tables *tab, float *out, uint64_t *hot, float thr,
-                        int keep) {
+                        int keep, uint32_t *qmax) {
     switch (rows) {
-        case 1: timed_launch((k_stft_power<LOGMAG, 1, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 2: timed_launch((k_stft_power<LOGMAG, 2, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 4: timed_launch((k_stft_power<LOGMAG, 4, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        case 8: timed_launch((k_stft_power<LOGMAG, 8, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
-        default: timed_launch((k_stft_power<LOGMAG, 16, T>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep); break;
+        case 1: timed_launch((k_stft_power<LOGMAG, 1, T, QMAX>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep, qmax); break;
+        case 2: timed_launch((k_stft_power<LOGMAG, 2, T, QMAX>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep, qmax); break;
+        case 4: timed_launch((k_stft_power<LOGMAG, 4, T, QMAX>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep, qmax); break;
+        case 8: timed_launch((k_stft_power<LOGMAG, 8, T, QMAX>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep, qmax); break;
+        default: timed_launch((k_stft_power<LOGMAG, 16, T, QMAX>), g, b, 0, s, pcm, clips, n_clips, f0, total, n_waves, tab, out, hot, thr, keep, qmax); break;
     }
 }
 
 // total_frames = sum of the clips' frames, the first at absolute frame f0 (out = its power row),
 // total_strips = sum of ceil(F / kStftStrip) (strip mode), slots = resident K1 waves on the device (CUs x kStftWaves).
-// s16: pcm is int16 samples (ClipDesc::pcm_off counts samples either way); the log-magnitude rows are float-only
+// s16: pcm is int16 samples (ClipDesc::pcm_off counts samples either way); the log-magnitude rows are float-only.
+// qmax (FPSPEC 5.1): null, or the clips' words (zeroed by the caller) that receive the bit pattern of max Q per clip
 void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
                        int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
-                       uint64_t *hot, float thr, bool keep_power, hipStream_t s) {
+                       uint64_t *hot, float thr, bool keep_power, uint32_t *qmax, hipStream_t s) {
     if (total_frames <= 0) return;
     // one round of equal ranges. A wave reloads its 16-row ring once per segment, so large batches keep
     // >= kStftStrip frames per wave; a batch smaller than that spreads over >= kK1MinFrames-frame ranges
@@ -512,13 +540,18 @@ void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_c
     const int64_t total = total_frames;
     const dim3 g((unsigned)((n_waves + kStftWaves - 1) / kStftWaves)), b(kStftWaves * 64);
     const float *f32 = static_cast<const float *>(pcm);
-    if (logmag) launch_rows<true>(hop / 128, g, b, s, f32, clips, n_clips, f0, total, n_waves, tab, out, nullptr, thr, 1);
-    else if (s16)
-        launch_rows<false>(hop / 128, g, b, s, static_cast<const int16_t *>(pcm), clips, n_clips, f0, total, n_waves, tab,
-                           out, hot, 4.0f * thr, keep_power ? 1 : 0);
-    else  // the power plane holds 4P (see the real split): hot blocks are those with 4P > 4 thr
-        launch_rows<false>(hop / 128, g, b, s, f32, clips, n_clips, f0, total, n_waves, tab, out, hot, 4.0f * thr,
-                           keep_power ? 1 : 0);
+    const float thr4 = 4.0f * thr;  // the power plane holds 4P (see the real split): hot blocks are those with 4P > 4 thr
+    const int keep = keep_power ? 1 : 0, rows = hop / 128;
+    auto go = [&](auto qm, auto *p) {
+        launch_rows<false, decltype(qm)::value>(rows, g, b, s, p, clips, n_clips, f0, total, n_waves, tab, out, hot, thr4, keep,
+                                                qmax);
+    };
+    if (logmag)
+        launch_rows<true, false>(rows, g, b, s, f32, clips, n_clips, f0, total, n_waves, tab, out, nullptr, thr, 1, nullptr);
+    else if (s16 && qmax) go(std::true_type{}, static_cast<const int16_t *>(pcm));
+    else if (s16) go(std::false_type{}, static_cast<const int16_t *>(pcm));
+    else if (qmax) go(std::true_type{}, f32);
+    else go(std::false_type{}, f32);
 }
 
 }  // namespace aid

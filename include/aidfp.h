@@ -67,7 +67,12 @@ typedef struct aid_config {
     int32_t min_match;     /* query: 0 = FPSPEC default 10 (distinct query anchor frames, FPSPEC v1 7) */
     int32_t max_results;   /* query: 0 = FPSPEC default 50 */
     int32_t flags;         /* AID_FLAG_* (0 = default) */
-    int32_t reserved[9];
+    float peak_rel;        /* FPSPEC 5.1: 0 = off (default); else r in [2^-60, 1): per clip of an extraction call the peak
+                              threshold is thr_c = max(peak_threshold, r * Pmax_c), Pmax_c = the clip's largest power
+                              over all frames and bins (a NaN never raises it; +0 for a clip without frames), and
+                              peak_threshold is the absolute floor. r = 10^(-top_db / 10) for "top_db below the
+                              loudest bin". Took the first reserved word: the struct stays 64 bytes, ABI version 1 */
+    int32_t reserved[8];
 } aid_config;
 
 /* aid_config.flags: keep the whole power plane of an extraction for aid_result_power. Without it
@@ -155,6 +160,11 @@ int aid_result_device(aid_engine *e, const aid_hash **records, const int64_t **c
    power rows [F][1024] fp32 of clip `clip` (needs AID_FLAG_KEEP_POWER); peak bitmask [F][16] uint64. */
 int aid_result_power(aid_engine *e, int32_t clip, float *out, int64_t cap_floats);
 int aid_result_peakmask(aid_engine *e, int32_t clip, uint64_t *out, int64_t cap_words);
+/* Effective peak threshold thr_c of every clip of the last extraction (host array of n_clips floats; FPSPEC 5.1).
+   With peak_rel = 0 it is peak_threshold for every clip. Synchronises. Every route that extracts (aid_extract*,
+   aid_query_pcm*, aid_query_windows*, aid_exact_lane*, the stream bank's windows) applies the engine's rule; a
+   clip is one extraction unit: a track, a query clip, one sub-window or one stream window. */
+int aid_result_thresholds(aid_engine *e, float *out);
 
 /* Log-magnitude spectrogram 10*log10(P + 1e-10) of one host clip: out[F][1024] (host). */
 int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int64_t cap_floats);
