@@ -301,7 +301,7 @@ class Engine:
     FORCE = {"k5_path": L.AID_FORCE_K5_PATH, "k5_parts": L.AID_FORCE_K5_PARTS, "k5_batch": L.AID_FORCE_K5_BATCH,
              "k2_strips_x100": L.AID_FORCE_K2_STRIPS_X100, "k4_build": L.AID_FORCE_K4_BUILD,
              "exchange_fail": L.AID_FORCE_EXCHANGE_FAIL, "lane_gather": L.AID_FORCE_LANE_GATHER,
-             "plane_rows": L.AID_FORCE_PLANE_ROWS}
+             "plane_rows": L.AID_FORCE_PLANE_ROWS, "k2_width": L.AID_FORCE_K2_WIDTH}
 
     def force(self, what: str, value: int) -> None:
         """Test hook (aid_engine_force): pin one of the engine's own code paths, e.g. force("k5_path", 2)."""
@@ -456,12 +456,13 @@ class Engine:
         return {"postings": n.value, "live": live.value, "tracks": nt.value}
 
     def match_stats(self, reset: bool = False) -> dict:
-        """Cumulative K5 counters (aid_match_stats): queries, votes, postings read, path split, records."""
-        out = np.zeros(13, dtype=np.int64)
-        check(self._lib.aid_match_stats(self._h, _p(out), 13, 1 if reset else 0))
+        """Cumulative K5 counters (aid_match_stats): queries, votes, postings read, path split, records; and the K2
+        width and strip count of the last extraction call (not counters)."""
+        out = np.zeros(15, dtype=np.int64)
+        check(self._lib.aid_match_stats(self._h, _p(out), 15, 1 if reset else 0))
         return dict(zip(("queries", "votes", "posting_reads", "queries_lds", "queries_global", "records", "sig_reads",
                          "lds_path_workgroups_per_cu", "fallback_heavy", "fallback_table", "fallback_distinct",
-                         "fallback_tracks", "fallback_rows"), (int(x) for x in out)))
+                         "fallback_tracks", "fallback_rows", "k2_width", "k2_strips"), (int(x) for x in out)))
 
     # ---- PCM front-end (FPSPEC 8): downmix + resample, device buffers ----
     def resample_len(self, n: int, sr_in: int, sr_out: int) -> int:

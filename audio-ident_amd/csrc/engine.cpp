@@ -26,13 +26,14 @@ namespace aid {
 void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
                        int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
                        uint64_t *hot, float thr, bool keep_power, uint32_t *qmax, hipStream_t s);
-int peak_pick_blocks_per_cu();
-void launch_peak_pick(const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
+int peak_pick_blocks_per_cu(int width);
+void launch_peak_pick(int width, const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
                       int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
                       const uint32_t *clip_qmax, float rel, hipStream_t s);
 void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
                       int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
-                      uint64_t *k2_cold_host, uint32_t k2_waves, bool one_chunk_each, hipStream_t s);
+                      uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips, bool one_chunk_each,
+                      hipStream_t s);
 void launch_synth(float *out, const uint32_t *tracks, const int64_t *starts, int n_clips, int64_t n, int sr,
                   int noise_a, uint32_t salt, int fmax_hz, bool envelope, const int16_t *sin_tab, hipStream_t s);
 int64_t resample_lds_floats(int up, int down, int J);
@@ -190,9 +191,14 @@ struct aid_engine {
     // FPSPEC 5.1 (cfg.peak_rel > 0): per clip of the call, the bit pattern of max Q over its plane. Zeroed on the
     // call's stream before the first K1, raised by K1's atomics, read by K2 and aid_result_thresholds
     DevBuf<uint32_t> clip_qmax;
-    DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64), summed and reset by K3
-    uint64_t *h_cold = nullptr;      // pinned, host-mapped: K3 stores (cold waves | waves << 32) of the last K2 here
+    DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3
+    // pinned, host-mapped, two words: K3 stores (cold waves | waves << 32) and (twice-walked strips | strips << 32) of
+    // the last K2 here; waves / strips is the width that K2 ran at
+    uint64_t *h_cold = nullptr;
     uint64_t *h_cold_dev = nullptr;  // its device address
+    int k2_width_force = 0;          // aid_engine_force K2_WIDTH: 2 or 4 quarter waves per K2 workgroup; 0 = adaptive
+    int k2_width = 4;                // the adaptive choice (extract_locked); also the width of the last call
+    int k2_hold = 0;                 // calls left at width 4 after a fall-back from width 2 (hysteresis)
     double k2_slots_x = 0.0;         // aid_engine_force K2_STRIPS: fixed strips per slot; 0 = adaptive (extract_locked)
     DevBuf<ClipDesc> desc;
     DevBuf<int64_t> chunk_counts;
@@ -283,7 +289,7 @@ struct aid_engine {
     std::vector<int64_t> clip_frames;
     int n_clips = 0;
     int64_t total_frames = 0, total_strips = 0, total_chunks = 0, total_records = 0;
-    int64_t k2_slots = 1;  // resident K2 workgroups on the device (CUs x blocks per CU)
+    int64_t k2_slots[2] = {1, 1};  // resident K2 workgroups on the device (CUs x blocks per CU) at width 2, 4
     int64_t k1_slots = 1;  // resident K1 waves (CUs x kStftWaves: one K1 workgroup per CU)
     int k5_path = 0;       // aid_engine_force K5_PATH: 0 auto, 1 LDS fast path first, 2 global path only (tests)
     int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
@@ -440,7 +446,7 @@ int aid_engine_create(const aid_config *cfg, aid_engine **out) {
     aid_engine *e = new aid_engine();
     e->cfg = c;
     e->device = dev;
-    e->k2_slots = (int64_t)prop.multiProcessorCount * peak_pick_blocks_per_cu();
+    for (int w = 0; w < 2; ++w) e->k2_slots[w] = (int64_t)prop.multiProcessorCount * peak_pick_blocks_per_cu(2 + 2 * w);
     e->k1_slots = (int64_t)prop.multiProcessorCount * kStftWaves;
     // blocking stream: ordered against the legacy default stream (torch's default), so device
     // buffers the caller filled there without a stream handle are complete before NULL-stream calls
@@ -609,6 +615,10 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
             e->k2_slots_x = value / 100.0;
             e->desc_dev_for_key = nullptr;  // strip bases change: rebuild the descriptors
             return AID_OK;
+        case AID_FORCE_K2_WIDTH:
+            if (value != 0 && value != 2 && value != 4) return fail(AID_ERR_INVALID, "K2_WIDTH: 0 adaptive, 2 or 4");
+            e->k2_width_force = value;
+            return AID_OK;
         case AID_FORCE_K4_BUILD:
             if (value < 0 || value > 4)
                 return fail(AID_ERR_INVALID, "K4_BUILD: 0 default, 1 radix, 2 atomic, 3 rocPRIM, 4 radix with ballot ranks");
@@ -704,7 +714,8 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
     // a different stream than the previous call's: order against it the simple way
     if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
     // same clips, PCM location and strip length as the descriptors already on the device: no re-upload
-    // key: [offset, length] per clip, the PCM location, then the K2 strip length of every clip group (below)
+    // key: [offset, length] per clip, the PCM location, then the K2 strip length of every clip group and the K2 width
+    // the lengths were sized for (below)
     bool desc_same = e->desc_dev_for_key == e->desc.p && e->desc.p && e->desc_key.size() > 2 * (size_t)n_clips + 1 &&
                      e->desc_key[2 * n_clips] == loc;
     for (int c = 0; desc_same && c < n_clips; ++c)
@@ -728,11 +739,42 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
     // fraction c of cold waves counted in earlier calls (K3 stores it in pinned memory; read without a sync,
     // so it lags a few calls), the strips are made shorter and more numerous, 0.75 / (1 - c) per slot,
     // quantised to 1, 1.25, 1.5 (a stable key for the cached descriptors)
+    //
+    // K2 width (peaks.hip): 2-wave workgroups over bins 0..511 fit 8 to a CU, all of their waves working, where band-
+    // limited audio leaves a CU 4 four-wave workgroups with two cold waves each; but they walk a strip a second time
+    // for bins 512..1023 when its upper half is hot, and K2 ends with its slowest workgroup: with 2 full-band clips
+    // among 256 (0.8 % of the strips walked twice) width 2 already took 0.196 ms against 0.118 at width 4, against
+    // 0.092 / 0.117 with none (profiles/k2_width_ab.txt). So width 2 is for calls in which no strip is walked twice.
+    // K2 counts those strips at width 2, K3 stores the count beside the cold one. From width 4 (the start) the choice
+    // goes to 2 when the cold count of a width-4 call says that there would be none: a strip needs no second walk
+    // exactly when its two upper quarter waves are strip-cold, so none does when half of all waves or more were
+    // cold (cold waves of the lower quarters can overstate this; the count at width 2 then corrects it). From width
+    // 2 it goes back to 4 as soon as a strip was walked twice, and stays there for kK2Hold calls, so a mixed workload
+    // does not flap: one slow call in 64. Counts of a launch at another width than the one in use are not applied
+    // (the words lag a few calls). Results never depend on the width or the strip length. At width 2 nothing exits on
+    // the audio it is chosen for: 1 strip per slot (1.25: K2 0.111 against 0.093 ms).
+    constexpr int kK2Hold = 64;
+    const uint64_t cw = e->h_cold ? *reinterpret_cast<volatile uint64_t *>(e->h_cold) : 0;
+    const uint64_t sw = e->h_cold ? *reinterpret_cast<volatile uint64_t *>(e->h_cold + 1) : 0;
+    const int seen_width = (sw >> 32) ? (int)((cw >> 32) / (sw >> 32)) : 0;  // of the launch that was counted
+    int width = e->k2_width_force;
+    if (!width) {
+        if (e->k2_width == 4) {
+            if (e->k2_hold > 0) --e->k2_hold;
+            else if (seen_width == 4 && 2 * (uint64_t)(uint32_t)cw >= (cw >> 32)) e->k2_width = 2;
+        } else if (seen_width == 2 && (uint32_t)sw > 0) {
+            e->k2_width = 4;
+            e->k2_hold = kK2Hold;
+        }
+        width = e->k2_width;
+    } else {
+        e->k2_width = width;
+    }
+    const int64_t k2_slots = e->k2_slots[width == 2 ? 0 : 1];
     double kx = e->k2_slots_x;
     if (kx <= 0.0) {
         kx = 1.0;
-        const uint64_t cw = e->h_cold ? *reinterpret_cast<volatile uint64_t *>(e->h_cold) : 0;
-        if (cw >> 32) {
+        if (width == 4 && seen_width == 4) {
             const double c = std::min(1.0, (double)(uint32_t)cw / (double)(cw >> 32));
             kx = c >= 0.45 ? 1.5 : c >= 0.3 ? 1.25 : 1.0;
         }
@@ -761,9 +803,10 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
     std::vector<int64_t> gfirst(n_groups), gframes(n_groups, 0), gstrips(n_groups, 0), gk(n_groups, 0);
     for (int g = 0; g < n_groups; ++g)  // K2 strips per resident slot, per group (strip_base restarts at 0 in each)
         glen[g] = peak_strip_len(e->clip_frames.data() + gstart[g], gstart[g + 1] - gstart[g],
-                                 std::max<int64_t>(1, (int64_t)(e->k2_slots * kx)));
+                                 std::max<int64_t>(1, (int64_t)(k2_slots * kx)));
     // strip bases follow the groups and their strip lengths: (first clip, strip length) per group in the key
-    desc_same = desc_same && e->desc_key.size() == 2 * (size_t)n_clips + 1 + 2 * (size_t)n_groups;
+    desc_same = desc_same && e->desc_key.size() == 2 * (size_t)n_clips + 2 + 2 * (size_t)n_groups &&
+                e->desc_key.back() == width;
     for (int g = 0; desc_same && g < n_groups; ++g)
         desc_same = e->desc_key[2 * n_clips + 1 + 2 * g] == gstart[g] && e->desc_key[2 * n_clips + 2 + 2 * g] == glen[g];
     for (int c = 0, g = 0; c < n_clips; ++c) {
@@ -813,12 +856,12 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
         if (n_clips > 0) HIP_TRY(hipMemsetAsync(e->clip_qmax.p, 0, sizeof(uint32_t) * (size_t)n_clips, s));
     }
     if (!e->k2_cold.p) {
-        HIP_TRY(e->k2_cold.reserve(64));
-        HIP_TRY(hipMemsetAsync(e->k2_cold.p, 0, 64 * sizeof(uint32_t), s));
+        HIP_TRY(e->k2_cold.reserve(128));
+        HIP_TRY(hipMemsetAsync(e->k2_cold.p, 0, 128 * sizeof(uint32_t), s));
     }
     if (!e->h_cold) {
-        HIP_TRY(hipHostMalloc((void **)&e->h_cold, sizeof(uint64_t), hipHostMallocMapped));
-        *e->h_cold = 0;
+        HIP_TRY(hipHostMalloc((void **)&e->h_cold, 2 * sizeof(uint64_t), hipHostMallocMapped));
+        e->h_cold[0] = e->h_cold[1] = 0;
         HIP_TRY(hipHostGetDevicePointer((void **)&e->h_cold_dev, e->h_cold, 0));
     }
     HIP_TRY(e->chunk_counts.reserve((size_t)chunks + 1));
@@ -853,6 +896,7 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
             e->desc_key.push_back(gstart[g]);
             e->desc_key.push_back(glen[g]);
         }
+        e->desc_key.push_back(width);
         e->desc_dev_for_key = e->desc.p;
     }
     if (empty_clip || frames == 0) HIP_TRY(hipMemsetAsync(e->counts.p, 0, sizeof(int64_t) * ((size_t)n_clips + 1), s));
@@ -879,7 +923,7 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
             }
             {
                 ProfScope ps(e, AID_K_PEAKS, s, true);
-                launch_peak_pick(e->power.p, e->desc.p + ca, ng, gfirst[g], gstrips[g], glen[g], e->cfg.peak_threshold,
+                launch_peak_pick(width, e->power.p, e->desc.p + ca, ng, gfirst[g], gstrips[g], glen[g], e->cfg.peak_threshold,
                                  e->hotw.p, e->mask.p, e->k2_cold.p, rel ? e->clip_qmax.p + ca : nullptr,
                                  e->cfg.peak_rel, s);
             }
@@ -887,13 +931,13 @@ static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int6
         if (multi_chunk) {  // some clip spans several K3 chunks: their bases need the COUNT pass
             ProfScope ps(e, AID_K_LANDMARK_COUNT, s, true);
             launch_landmarks(e->mask.p, e->desc.p, n_clips, chunks, e->chunk_counts.p, e->records.p, e->counts.p,
-                             false, nullptr, nullptr, 0u, one_chunk_each, s);
+                             false, nullptr, nullptr, 0u, 0u, one_chunk_each, s);
         }
         {
             ProfScope ps(e, AID_K_LANDMARK_WRITE, s, true);
             launch_landmarks(e->mask.p, e->desc.p, n_clips, chunks, e->chunk_counts.p, e->records.p, e->counts.p,
-                             true, e->h_cold_dev ? e->k2_cold.p : nullptr, e->h_cold_dev, (uint32_t)(4 * strips),
-                             one_chunk_each, s);
+                             true, e->h_cold_dev ? e->k2_cold.p : nullptr, e->h_cold_dev, (uint32_t)(width * strips),
+                             (uint32_t)strips, one_chunk_each, s);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1769,11 +1813,11 @@ int aid_index_finalize(aid_engine *e) {
 int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
     if (!e || (n > 0 && !out)) return fail(AID_ERR_INVALID, "aid_match_stats: bad argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    const int64_t v[13] = {e->st_queries,     e->st_votes,   e->st_post_reads, e->st_q_lds,
+    const int64_t v[15] = {e->st_queries,     e->st_votes,   e->st_post_reads, e->st_q_lds,
                            e->st_q_global,    e->st_records, e->st_sig_reads,  (int64_t)match_lds_blocks_per_cu(),
                            e->st_fb_reason[0], e->st_fb_reason[1], e->st_fb_reason[2], e->st_fb_reason[3],
-                           e->st_fb_reason[4]};
-    for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
+                           e->st_fb_reason[4], e->k2_width, e->total_strips};
+    for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
     if (reset) {
         e->st_queries = e->st_votes = e->st_post_reads = e->st_q_lds = e->st_q_global = e->st_records = e->st_sig_reads = 0;
         for (auto &r : e->st_fb_reason) r = 0;

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ 
                                                   int n_clips, int64_t total_chunks, int64_t *__restrict__ chunk_counts,
                                                   uint64_t *__restrict__ records, int64_t *__restrict__ clip_counts,
                                                   uint32_t *__restrict__ k2_cold, uint64_t *__restrict__ k2_cold_host,
-                                                  uint32_t k2_waves, int one_chunk_each) {
+                                                  uint32_t k2_waves, uint32_t k2_strips, int one_chunk_each) {
     __shared__ uint32_t plist[kHashChunkPeakCap];
     __shared__ uint32_t foff[kHashChunk + kZoneDT + 2];
     __shared__ int64_t scan_tmp[kK3];
@@ -64,11 +64,20 @@ __global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ 
     if (WRITE && k2_cold && blockIdx.x == 0 && tid < 64) {
         // K2's strip-cold wave count (peaks.hip) and the wave count of that same launch, stored together as
         // one 8-byte word in host-mapped memory for the next call's strip sizing (no sync: a stale pair only
-        // delays the adaptation), then the counters are reset for the next K2
-        uint32_t c = k2_cold[tid];
+        // delays the adaptation), then the counters are reset for the next K2. A second word holds the strips that
+        // width-2 workgroups walked twice (counters 64..127) and the strip count, for the next call's width
+        uint32_t c = k2_cold[tid], c2 = k2_cold[64 + tid];
         k2_cold[tid] = 0u;
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-        if (tid == 0) *reinterpret_cast<volatile uint64_t *>(k2_cold_host) = (uint64_t)c | ((uint64_t)k2_waves << 32);
+        k2_cold[64 + tid] = 0u;
+        for (int o = 32; o > 0; o >>= 1) {
+            c += __shfl_xor(c, o);
+            c2 += __shfl_xor(c2, o);
+        }
+        if (tid == 0) {
+            volatile uint64_t *h = reinterpret_cast<volatile uint64_t *>(k2_cold_host);
+            h[0] = (uint64_t)c | ((uint64_t)k2_waves << 32);
+            h[1] = (uint64_t)c2 | ((uint64_t)k2_strips << 32);
+        }
     }
     if (chunk >= total_chunks) return;
     int lo = 0, hi = n_clips - 1;
@@ -212,16 +221,17 @@ __global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ 
 
 void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
                       int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
-                      uint64_t *k2_cold_host, uint32_t k2_waves, bool one_chunk_each, hipStream_t s) {
+                      uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips, bool one_chunk_each,
+                      hipStream_t s) {
     if (total_chunks <= 0) return;
     if (write)
         timed_launch(k_landmarks<true>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, clips, n_clips,
                            total_chunks, chunk_counts, records, clip_counts, k2_cold, k2_cold_host, k2_waves,
-                     one_chunk_each ? 1 : 0);
+                     k2_strips, one_chunk_each ? 1 : 0);
     else
         timed_launch(k_landmarks<false>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, clips, n_clips,
                            total_chunks, chunk_counts, records, clip_counts, (uint32_t *)nullptr, (uint64_t *)nullptr, 0u,
-                     one_chunk_each ? 1 : 0);
+                     0u, one_chunk_each ? 1 : 0);
 }
 
 }  // namespace aid

@@ -112,6 +112,8 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
                                       of extracting them in place (A/B) */
 #define AID_FORCE_PLANE_ROWS 8     /* 0 default (786,432), else power rows per K1 -> K2 clip group of one extraction
                                       call (tests: small calls split into several groups) */
+#define AID_FORCE_K2_WIDTH 9       /* 0 adaptive, else 2 or 4 quarter waves per K2 workgroup (width 2: bins 0..511 per
+                                      walk, a second walk over a strip whose upper half is hot) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
@@ -228,7 +230,8 @@ int aid_index_finalize(aid_engine *e);
    LDS path read (twice per vote: its counting and insert passes; the insert pass also reads the 8-B posting of a
    vote whose bucket is hot), [7] resident LDS-path workgroups per CU (an occupancy query, not a counter),
    [8..12] queries the LDS path handed to the global path, by reason: above 2^18 votes, (track, d) table full,
-   distinct-frame set full, track table full, more rows than its staging holds. */
+   distinct-frame set full, track table full, more rows than its staging holds. Not counters either: [13] the K2
+   width (AID_FORCE_K2_WIDTH) and [14] the K2 strips of the engine's last extraction call. */
 int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
 /* n_postings = stored postings, n_live = postings in the built CSR (-1 if stale), n_tracks = max id + 1 */
 int aid_index_stats(aid_engine *e, int64_t *n_postings, int64_t *n_live, uint32_t *n_tracks);
