@@ -24,6 +24,7 @@ AID_SYNTH_STATIONARY = 1
 AID_SYNTH_ASYNC = 2
 (AID_FORCE_K5_PATH, AID_FORCE_K5_PARTS, AID_FORCE_K5_BATCH, AID_FORCE_K2_STRIPS_X100, AID_FORCE_K4_BUILD,
  AID_FORCE_EXCHANGE_FAIL, AID_FORCE_LANE_GATHER, AID_FORCE_PLANE_ROWS, AID_FORCE_K2_WIDTH) = 1, 2, 3, 4, 5, 6, 7, 8, 9
+AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK = 10, 11
 AID_K_STFT, AID_K_PEAKS, AID_K_LANDMARK_COUNT, AID_K_LANDMARK_WRITE, AID_K_SYNTH, AID_K_MATCH = range(6)
 AID_K_COUNT = 12
 KERNEL_NAMES = ["stft_power", "peak_pick", "landmark_count", "landmark_write", "synth", "match", "resample",
@@ -74,6 +75,26 @@ class AidExactRow(ctypes.Structure):
         ("aligned_hashes", ctypes.c_int32),
         ("offset_seconds", ctypes.c_double),
         ("confidence", ctypes.c_double),
+    ]
+
+
+class AidVecHit(ctypes.Structure):
+    _fields_ = [
+        ("entry", ctypes.c_uint32),
+        ("track", ctypes.c_uint32),
+        ("chunk_index", ctypes.c_int32),
+        ("score", ctypes.c_float),
+        ("offset_sec", ctypes.c_double),
+    ]
+
+
+class AidVibeRow(ctypes.Structure):
+    _fields_ = [
+        ("track", ctypes.c_uint32),
+        ("chunk_count", ctypes.c_int32),
+        ("final_score", ctypes.c_double),
+        ("base_score", ctypes.c_double),
+        ("diversity_bonus", ctypes.c_double),
     ]
 
 
@@ -147,6 +168,17 @@ SIGNATURES = [
     ("aid_dedup_count", ctypes.c_int, [P, P, P]),
     ("aid_dedup_scan", ctypes.c_int, [P, P, P, P, I32, P, P]),
     ("aid_dedup_pairs", ctypes.c_int, [P, P, P, P, P, I32, P]),
+    ("aid_vec_reset", ctypes.c_int, [P, I32]),
+    ("aid_vec_add", ctypes.c_int, [P, P, P, P, P, I64, I32]),
+    ("aid_vec_remove", ctypes.c_int, [P, ctypes.c_uint32]),
+    ("aid_vec_compact", ctypes.c_int, [P, P]),
+    ("aid_vec_count", ctypes.c_int, [P, P, P, P]),
+    ("aid_vec_search", ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
+    ("aid_vec_scores", ctypes.c_int, [P, P, I32, I32, P, I64]),
+    ("aid_vec_aggregate", ctypes.c_int, [P, P, P, I32, I32, ctypes.c_double, P, ctypes.c_double, I32, P, P]),
+    ("aid_vibe_lane", ctypes.c_int, [P, P, I32, I32, I32, I32, ctypes.c_double, P, ctypes.c_double, I32, P, P, P]),
+    ("aid_vec_save", ctypes.c_int, [P, ctypes.c_char_p]),
+    ("aid_vec_load", ctypes.c_int, [P, ctypes.c_char_p]),
     ("aid_profile_enable", ctypes.c_int, [P, I32]),
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),

@@ -1,0 +1,262 @@
+"""The vibe lane on the GPU -- drop-in for the Qdrant side of audio-ident-service.
+
+The reference keeps 512-dim CLAP chunk embeddings in a Qdrant collection (cosine distance, HNSW over int8
+scalar quantisation, app/audio/qdrant_setup.py:50-64), asks it for the 50 nearest chunks of a query
+(`_query_qdrant`, app/search/vibe.py:164-218) and folds them into track scores (`aggregate_chunk_hits`,
+app/search/aggregation.py:63-138). Here the catalog lives in HBM (`VectorIndex`, C ABI aid_vec_*), one call scores
+a whole batch of queries against all of it exactly (K9, csrc/vector.hip) and aggregates on the device
+(aid_vibe_lane). The arithmetic is pinned by spec/FPSPEC.md 9: the same scores, hits and rows on every run.
+
+The CLAP model stays with the caller: embeddings come in as float vectors (numpy, or torch tensors already on the
+device, which are read in place). So do the metadata lookup and `similarity = min(final_score, 1.0)`
+(vibe.py:131-159).
+"""
+
+from __future__ import annotations
+
+import ctypes
+import threading
+import uuid
+from dataclasses import dataclass
+from typing import Sequence
+
+import numpy as np
+
+from . import _lib as L
+from ._lib import AidVecHit, AidVibeRow, check
+
+VEC_NO_TRACK = 0xFFFFFFFF
+HIT_DTYPE = np.dtype([("entry", "<u4"), ("track", "<u4"), ("chunk_index", "<i4"), ("score", "<f4"), ("offset_sec", "<f8")])
+ROW_DTYPE = np.dtype([("track", "<u4"), ("chunk_count", "<i4"), ("final_score", "<f8"), ("base_score", "<f8"),
+                      ("diversity_bonus", "<f8")])
+assert HIT_DTYPE.itemsize == ctypes.sizeof(AidVecHit) and ROW_DTYPE.itemsize == ctypes.sizeof(AidVibeRow)
+
+
+@dataclass(frozen=True)
+class ChunkHit:
+    """aggregation.py:25-39."""
+
+    track_id: uuid.UUID
+    score: float
+    chunk_index: int
+    offset_sec: float
+
+
+@dataclass(frozen=True)
+class TrackResult:
+    """aggregation.py:42-60. `top_chunk_scores` stays empty: the lane returns the aggregate, not the chunks."""
+
+    track_id: uuid.UUID
+    final_score: float
+    base_score: float
+    diversity_bonus: float
+    chunk_count: int
+    top_chunk_scores: tuple = ()
+
+
+def _p(a: np.ndarray) -> ctypes.c_void_p:
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _vectors(x, dim: int):
+    """(pointer, n, location, keep-alive) of [n][dim] float32 vectors: a numpy array (host) or a torch tensor
+    (on the device: read in place; on the host: through numpy)."""
+    if hasattr(x, "data_ptr"):  # torch tensor
+        import torch
+
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if x.shape[-1] != dim:
+            raise ValueError(f"embeddings must be [n][{dim}]")
+        if x.is_cuda:
+            x = x.to(torch.float32).contiguous()
+            torch.cuda.current_stream(x.device).synchronize()  # the engine reads it on its own stream
+            return ctypes.c_void_p(x.data_ptr()), int(x.shape[0]), L.AID_PCM_DEVICE, x
+        x = x.detach().numpy()
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+    if a.ndim != 2 or a.shape[1] != dim:
+        raise ValueError(f"embeddings must be [n][{dim}]")
+    return _p(a), int(a.shape[0]), L.AID_PCM_HOST, a
+
+
+class VectorIndex:
+    """Device-resident catalog of chunk embeddings; keeps the engine id <-> uuid.UUID map as ContentIndex does."""
+
+    def __init__(self, engine, dim: int = 512):
+        self.eng = engine
+        self.dim = int(dim)
+        self._ids: list = []   # engine track id -> caller id
+        self._num: dict = {}   # caller id -> engine track id
+        self._live: set = set()
+        self._lock = threading.Lock()
+        check(engine._lib.aid_vec_reset(engine._h, self.dim))
+
+    # -- catalog --
+    def _track(self, track_id) -> int:
+        t = self._num.get(track_id)
+        if t is None:
+            t = len(self._ids)
+            self._ids.append(track_id)
+            self._num[track_id] = t
+        return t
+
+    def upsert_track(self, track_id, embeddings, offsets, chunk_indices=None) -> int:
+        """Store one track's chunks (replacing the ones it had); returns how many."""
+        ptr, n, loc, keep = _vectors(embeddings, self.dim)
+        off = np.ascontiguousarray(offsets, dtype=np.float64)
+        ci = np.arange(n, dtype=np.int32) if chunk_indices is None else np.ascontiguousarray(chunk_indices, dtype=np.int32)
+        if len(off) != n or len(ci) != n:
+            raise ValueError("one offset and one chunk index per embedding")
+        with self._lock:
+            if track_id in self._live:
+                self._delete_locked(track_id)
+            if n == 0:
+                return 0
+            t = self._track(track_id)
+            tr = np.full(n, t, dtype=np.uint32)
+            if loc == L.AID_PCM_DEVICE:  # payload columns follow the vectors' location
+                import torch
+
+                dev = keep.device
+                cols = [torch.from_numpy(a).to(dev) for a in (tr.view(np.int32), ci, off)]
+                torch.cuda.current_stream(dev).synchronize()
+                args = [ctypes.c_void_p(c.data_ptr()) for c in cols]
+            else:
+                args = [_p(tr), _p(ci), _p(off)]
+            check(self.eng._lib.aid_vec_add(self.eng._h, ptr, args[0], args[1], args[2], n, loc))
+            self._live.add(track_id)
+        return n
+
+    def _delete_locked(self, track_id) -> None:
+        check(self.eng._lib.aid_vec_remove(self.eng._h, self._num[track_id]))
+        self._live.discard(track_id)
+
+    def delete_track(self, track_id) -> bool:
+        """Remove every chunk of a track; False if it has none (Qdrant's delete is a no-op then)."""
+        with self._lock:
+            if track_id not in self._live:
+                return False
+            self._delete_locked(track_id)
+            return True
+
+    def compact(self) -> int:
+        n = ctypes.c_int64()
+        check(self.eng._lib.aid_vec_compact(self.eng._h, ctypes.byref(n)))
+        return n.value
+
+    def counts(self) -> tuple[int, int]:
+        """(entries stored, entries live)."""
+        n, live, dim = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        check(self.eng._lib.aid_vec_count(self.eng._h, ctypes.byref(n), ctypes.byref(live), ctypes.byref(dim)))
+        return n.value, live.value
+
+    def __len__(self) -> int:
+        return self.counts()[1]
+
+    # -- queries --
+    def search_raw(self, embeddings, limit: int = 50) -> list[np.ndarray]:
+        """Per query a HIT_DTYPE array (engine ids), best first."""
+        ptr, nq, loc, _keep = _vectors(embeddings, self.dim)
+        hits = np.zeros((max(nq, 1), limit), dtype=HIT_DTYPE)
+        nh = np.zeros(max(nq, 1), dtype=np.int32)
+        check(self.eng._lib.aid_vec_search(self.eng._h, ptr, nq, loc, int(limit), _p(hits), _p(nh), None))
+        return [hits[q, : nh[q]].copy() for q in range(nq)]
+
+    def search(self, embeddings, limit: int = 50) -> list[list[ChunkHit]]:
+        """`_query_qdrant` for a batch of queries: per query the `limit` nearest chunks."""
+        ids = self._ids
+        return [[ChunkHit(ids[int(h["track"])], float(h["score"]), int(h["chunk_index"]), float(h["offset_sec"])) for h in hs]
+                for hs in self.search_raw(embeddings, limit)]
+
+    def vibe_raw(self, embeddings, max_results: int, exclude=None, threshold: float = 0.60, top_k_per_track: int = 3,
+                 diversity_weight: float = 0.05, limit: int = 50) -> list[np.ndarray]:
+        """Per query a ROW_DTYPE array (engine ids); exclude: per query an engine track id or VEC_NO_TRACK."""
+        ptr, nq, loc, _keep = _vectors(embeddings, self.dim)
+        rows = np.zeros((max(nq, 1), max_results), dtype=ROW_DTYPE)
+        nr = np.zeros(max(nq, 1), dtype=np.int32)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint32)
+        check(self.eng._lib.aid_vibe_lane(self.eng._h, ptr, nq, loc, int(limit), int(top_k_per_track),
+                                          float(diversity_weight), None if ex is None else _p(ex), float(threshold),
+                                          int(max_results), _p(rows), _p(nr), None))
+        return [rows[q, : nr[q]].copy() for q in range(nq)]
+
+    def vibe(self, embeddings, max_results: int, exact_match_track_ids: Sequence | None = None, threshold: float = 0.60,
+             top_k_per_track: int = 3, diversity_weight: float = 0.05, limit: int = 50) -> list[list[TrackResult]]:
+        """Steps 3-6 of run_vibe_lane (vibe.py:100-129) for a batch of query embeddings, in one engine call.
+        exact_match_track_ids: per query the track to leave out, or None."""
+        ex = None
+        if exact_match_track_ids is not None:
+            ex = [VEC_NO_TRACK if t is None else self._num.get(t, VEC_NO_TRACK) for t in exact_match_track_ids]
+        ids = self._ids
+        return [[TrackResult(ids[int(r["track"])], float(r["final_score"]), float(r["base_score"]),
+                             float(r["diversity_bonus"]), int(r["chunk_count"])) for r in rows]
+                for rows in self.vibe_raw(embeddings, max_results, ex, threshold, top_k_per_track, diversity_weight, limit)]
+
+    # -- persistence --
+    def save(self, path: str) -> None:
+        """The catalog to `path` (AIDFPVC1) and the id map beside it (`path`.ids, one id per line)."""
+        check(self.eng._lib.aid_vec_save(self.eng._h, str(path).encode()))
+        with open(str(path) + ".ids", "w") as f:
+            f.write("\n".join(str(i) for i in self._ids))
+
+    def load(self, path: str, parse=uuid.UUID) -> None:
+        with open(str(path) + ".ids") as f:
+            ids = [parse(s) for s in f.read().split("\n") if s]
+        check(self.eng._lib.aid_vec_load(self.eng._h, str(path).encode()))
+        n, live, dim = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        check(self.eng._lib.aid_vec_count(self.eng._h, ctypes.byref(n), ctypes.byref(live), ctypes.byref(dim)))
+        with self._lock:
+            self.dim = dim.value
+            self._ids = ids
+            self._num = {t: i for i, t in enumerate(ids)}
+            self._live = set()
+            if live.value:  # the tracks that still have a live entry: ask the catalog's own save file
+                hdr = 24
+                tiles = (n.value + 31) // 32
+                with open(path, "rb") as f:
+                    f.seek(hdr + tiles * 32 * self.dim * 4)
+                    tr = np.frombuffer(f.read(4 * n.value), dtype="<u4")
+                    f.seek(hdr + tiles * 32 * self.dim * 4 + 16 * n.value)
+                    dead = np.frombuffer(f.read(n.value), dtype=np.uint8)
+                self._live = {ids[int(t)] for t in np.unique(tr[dead == 0])}
+
+
+def aggregate_hits(engine, hit_lists: Sequence[np.ndarray], top_k_per_track: int = 3, diversity_weight: float = 0.05,
+                   exclude=None, threshold: float = -np.inf, max_out: int | None = None) -> list[np.ndarray]:
+    """aid_vec_aggregate: `aggregate_chunk_hits` over host hit lists (HIT_DTYPE arrays, engine ids), as the dedup
+    lane's pairs call replays reference fixtures without a search."""
+    nq = len(hit_lists)
+    hoff = np.zeros(nq + 1, dtype=np.int64)
+    if nq:
+        hoff[1:] = np.cumsum([len(h) for h in hit_lists])
+    hits = np.concatenate([np.asarray(h, dtype=HIT_DTYPE) for h in hit_lists]) if hoff[-1] else np.zeros(1, HIT_DTYPE)
+    hits = np.ascontiguousarray(hits)
+    if max_out is None:
+        max_out = max(1, max((len(h) for h in hit_lists), default=1))
+    rows = np.zeros((max(nq, 1), max_out), dtype=ROW_DTYPE)
+    nr = np.zeros(max(nq, 1), dtype=np.int32)
+    ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint32)
+    check(engine._lib.aid_vec_aggregate(engine._h, _p(hits), _p(hoff), nq, int(top_k_per_track), float(diversity_weight),
+                                        None if ex is None else _p(ex), float(threshold), int(max_out), _p(rows), _p(nr)))
+    return [rows[q, : nr[q]].copy() for q in range(nq)]
+
+
+# ---- async drop-ins with the reference's names and argument order: `client` is a VectorIndex ----
+
+async def upsert_track_embeddings(client: VectorIndex, track_id: uuid.UUID, chunks, metadata: dict | None = None) -> int:
+    """qdrant_setup.py:81-156. chunks: objects with .embedding, .offset_sec and .chunk_index (AudioChunk);
+    the metadata payload stays in the caller's database."""
+    if not chunks:
+        return 0
+    emb = np.stack([np.asarray(c.embedding, dtype=np.float32) for c in chunks])
+    return client.upsert_track(track_id, emb, [float(c.offset_sec) for c in chunks], [int(c.chunk_index) for c in chunks])
+
+
+async def delete_track_embeddings(client: VectorIndex, track_id: uuid.UUID) -> None:
+    """qdrant_setup.py:159-181."""
+    client.delete_track(track_id)
+
+
+async def query_chunks(client: VectorIndex, embedding, limit: int = 50) -> list[ChunkHit]:
+    """Stands in for `_query_qdrant` (vibe.py:164-218): the `limit` nearest chunks of one embedding."""
+    return client.search(np.asarray(embedding, dtype=np.float32)[None, :], limit)[0]

@@ -1,0 +1,83 @@
+// aidfp_vector.h -- the vector lane's catalog (spec/FPSPEC.md 9, K9): host state and entry points of
+// csrc/vector.hip. engine.cpp owns one VecCatalog per engine and calls these under the engine lock with the
+// engine's device current; every function returns AID_OK or an AID_ERR_* code and leaves its message in `err`.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/aidfp.h"
+
+namespace aid {
+
+constexpr int kVecMaxLimit = 1024;      // hits per query, and hits per list of aid_vec_aggregate
+constexpr int kVecQueryBatch = 64;      // queries per scan + selection pass: bounds the score and key scratch
+constexpr int kVecScanChunk = 1024;     // default catalog rows per scan workgroup (8 waves, 4 tiles each)
+constexpr int kVecMaxSlice = 1024;      // default entries per slice maximum of the threshold route
+constexpr int kVecCandCap = 4096;       // candidates per query of the threshold route (one sort in LDS)
+constexpr int kVecSelectSlice = 4096;   // default keys per selection workgroup (one bitonic sort in LDS)
+
+// Stored layout of a [rows][dim] matrix (catalog and query tiles alike): rows in tiles of 32, and within a tile
+// the float at (row i, k) sits at ((k >> 3) * 2 + (k & 1)) * 128 + i * 4 + ((k & 7) >> 1). Lane (i, h) of a wave
+// fetches the operands of four consecutive 32x32x2 MFMA steps (k = 8g + h + {0, 2, 4, 6}) with one aligned 16-byte
+// load, and the 64 lanes of a wave read 1 KB contiguous.
+inline size_t vec_layout_index(int64_t row, int k, int dim) {
+    return (size_t)(row >> 5) * 32 * dim + (size_t)(((k >> 3) * 2 + (k & 1)) * 128 + (int)(row & 31) * 4 + ((k & 7) >> 1));
+}
+
+template <typename T>
+struct VecBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    hipError_t reserve(size_t want);  // contents are lost on growth
+    void release();
+};
+
+struct VecCatalog {
+    int dim = 0;  // 0 until aid_vec_reset
+    int64_t n = 0, n_live = 0;
+    int64_t cap_rows = 0;  // multiple of 32; rows [n, cap_rows) of d_vecs are +0
+    float *d_vecs = nullptr;
+    VecBuf<uint32_t> d_track;
+    VecBuf<double> d_off;
+    VecBuf<uint8_t> d_dead;
+    std::vector<uint32_t> h_track;  // host mirror of the payload columns (hits are filled from it)
+    std::vector<int32_t> h_chunk;
+    std::vector<double> h_off;
+    std::vector<uint8_t> h_dead;
+    int force_path = 0;   // AID_FORCE_VEC_PATH
+    int force_chunk = 0;  // AID_FORCE_VEC_CHUNK
+    // scratch
+    VecBuf<float> d_raw, d_q, d_scores;
+    VecBuf<unsigned long long> d_keys0, d_keys1, d_cand;
+    VecBuf<uint32_t> d_smax, d_thr;
+    VecBuf<int32_t> d_ccnt;
+    VecBuf<uint32_t> d_hentry, d_htrack, d_excl;
+    VecBuf<float> d_hscore;
+    VecBuf<double> d_hoff;
+    VecBuf<int32_t> d_nhits, d_cnt, d_nout;
+    VecBuf<int64_t> d_start;
+    VecBuf<aid_vibe_row> d_rows;
+    std::string err;
+    void release_all();
+};
+
+int vec_reset(VecCatalog &c, int dim);
+int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index, const double *offset_sec,
+            int64_t n, int location, hipStream_t s);
+int vec_remove(VecCatalog &c, uint32_t track, hipStream_t s);
+int vec_compact(VecCatalog &c, int64_t *n_removed, hipStream_t s);
+int vec_search(VecCatalog &c, const float *queries, int nq, int location, int limit, aid_vec_hit *hits, int32_t *n_hits,
+               hipStream_t s);
+int vec_scores(VecCatalog &c, const float *queries, int nq, int location, float *out, int64_t cap, hipStream_t s);
+int vec_aggregate(VecCatalog &c, const aid_vec_hit *hits, const int64_t *hoff, int nq, int top_k, double weight,
+                  const uint32_t *exclude, double threshold, int max_out, aid_vibe_row *out, int32_t *n_out,
+                  hipStream_t s);
+int vec_lane(VecCatalog &c, const float *queries, int nq, int location, int limit, int top_k, double weight,
+             const uint32_t *exclude, double threshold, int max_out, aid_vibe_row *out, int32_t *n_out, hipStream_t s);
+int vec_save(VecCatalog &c, const char *path, hipStream_t s);
+int vec_load(VecCatalog &c, const char *path, hipStream_t s);
+
+}  // namespace aid

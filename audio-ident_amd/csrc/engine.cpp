@@ -20,6 +20,7 @@
 #include "../../include/aidfp.h"
 #include "aidfp_device.h"
 #include "aidfp_layout.h"
+#include "aidfp_vector.h"
 #include "resample_design.h"
 
 namespace aid {
@@ -270,6 +271,7 @@ struct aid_engine {
     DevBuf<uint32_t> dq_words, dq_words2;
     DevBuf<int64_t> dq_off, dq_off2, dq_idx, dq_pidx;
     DevBuf<double> dq_lo, dq_hi, dq_sim, dq_psim;
+    VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
     DevBuf<uint32_t> g_send, g_recv;   // all-gather: [3][max] SoA planes per rank
     DevBuf<uint32_t> x_tracks;
     size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
@@ -568,6 +570,7 @@ void aid_engine_destroy(aid_engine *e) {
     e->dq_hi.release();
     e->dq_sim.release();
     e->dq_psim.release();
+    e->vec.release_all();
     e->g_send.release();
     e->g_recv.release();
     e->x_tracks.release();
@@ -640,6 +643,15 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
         case AID_FORCE_PLANE_ROWS:
             if (value < 0) return fail(AID_ERR_INVALID, "PLANE_ROWS must be >= 0");
             e->plane_rows = value;
+            return AID_OK;
+        case AID_FORCE_VEC_PATH:
+            if (value < 0 || value > 2) return fail(AID_ERR_INVALID, "VEC_PATH: 0 auto, 1 MFMA, 2 VALU");
+            e->vec.force_path = value;
+            return AID_OK;
+        case AID_FORCE_VEC_CHUNK:
+            if (value != 0 && (value < 32 || value > 4096 || value % 32))
+                return fail(AID_ERR_INVALID, "VEC_CHUNK: 0 default, else a multiple of 32 in [32, 4096]");
+            e->vec.force_chunk = value;
             return AID_OK;
         default:
             return fail(AID_ERR_INVALID, "aid_engine_force: unknown path id");
@@ -1423,6 +1435,66 @@ int aid_dedup_pairs(aid_engine *e, const uint32_t *a, const int64_t *a_off, cons
     HIP_TRY(hipStreamSynchronize(s));
     return AID_OK;
 }
+
+// ---- vector lane (FPSPEC 9): thin wrappers over csrc/vector.hip, one critical section per call
+#define VEC_CALL(e, stream, call)                                                   \
+    do {                                                                            \
+        if (!(e)) return fail(AID_ERR_INVALID, "null engine");                      \
+        std::lock_guard<std::mutex> lk((e)->mu);                                    \
+        HIP_TRY(hipSetDevice((e)->device));                                         \
+        if ((e)->last_stream) HIP_TRY(hipStreamSynchronize((e)->last_stream));      \
+        hipStream_t s = (stream) ? (hipStream_t)(stream) : (e)->own_stream;         \
+        (void)s;                                                                    \
+        const int rc = (call);                                                      \
+        return rc ? fail(rc, (e)->vec.err) : AID_OK;                                \
+    } while (0)
+
+int aid_vec_reset(aid_engine *e, int32_t dim) { VEC_CALL(e, nullptr, vec_reset(e->vec, dim)); }
+
+int aid_vec_add(aid_engine *e, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index,
+                const double *offset_sec, int64_t n, int32_t location) {
+    VEC_CALL(e, nullptr, vec_add(e->vec, vecs, tracks, chunk_index, offset_sec, n, location, s));
+}
+
+int aid_vec_remove(aid_engine *e, uint32_t track) { VEC_CALL(e, nullptr, vec_remove(e->vec, track, s)); }
+
+int aid_vec_compact(aid_engine *e, int64_t *n_removed) { VEC_CALL(e, nullptr, vec_compact(e->vec, n_removed, s)); }
+
+int aid_vec_count(aid_engine *e, int64_t *n_entries, int64_t *n_live, int32_t *dim) {
+    if (!e) return fail(AID_ERR_INVALID, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n_entries) *n_entries = e->vec.n;
+    if (n_live) *n_live = e->vec.n_live;
+    if (dim) *dim = e->vec.dim;
+    return AID_OK;
+}
+
+int aid_vec_search(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                   aid_vec_hit *hits, int32_t *n_hits, void *stream) {
+    VEC_CALL(e, stream, vec_search(e->vec, queries, nq, location, limit, hits, n_hits, s));
+}
+
+int aid_vec_scores(aid_engine *e, const float *queries, int32_t nq, int32_t location, float *out, int64_t cap) {
+    VEC_CALL(e, nullptr, vec_scores(e->vec, queries, nq, location, out, cap, s));
+}
+
+int aid_vec_aggregate(aid_engine *e, const aid_vec_hit *hits, const int64_t *hoff, int32_t nq, int32_t top_k_per_track,
+                      double diversity_weight, const uint32_t *exclude, double threshold, int32_t max_out,
+                      aid_vibe_row *out, int32_t *n_out) {
+    VEC_CALL(e, nullptr, vec_aggregate(e->vec, hits, hoff, nq, top_k_per_track, diversity_weight, exclude, threshold,
+                                       max_out, out, n_out, s));
+}
+
+int aid_vibe_lane(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                  int32_t top_k_per_track, double diversity_weight, const uint32_t *exclude, double threshold,
+                  int32_t max_out, aid_vibe_row *out, int32_t *n_out, void *stream) {
+    VEC_CALL(e, stream, vec_lane(e->vec, queries, nq, location, limit, top_k_per_track, diversity_weight, exclude,
+                                 threshold, max_out, out, n_out, s));
+}
+
+int aid_vec_save(aid_engine *e, const char *path) { VEC_CALL(e, nullptr, vec_save(e->vec, path, s)); }
+
+int aid_vec_load(aid_engine *e, const char *path) { VEC_CALL(e, nullptr, vec_load(e->vec, path, s)); }
 
 int aid_profile_enable(aid_engine *e, int32_t on) {
     if (!e) return fail(AID_ERR_INVALID, "null engine");

@@ -114,6 +114,9 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
                                       call (tests: small calls split into several groups) */
 #define AID_FORCE_K2_WIDTH 9       /* 0 adaptive, else 2 or 4 quarter waves per K2 workgroup (width 2: bins 0..511 per
                                       walk, a second walk over a strip whose upper half is hot) */
+#define AID_FORCE_VEC_PATH 10      /* K9 scan: 0 auto (MFMA), 1 MFMA, 2 VALU (explicit fmaf, one pair per lane) */
+#define AID_FORCE_VEC_CHUNK 11     /* 0 default, else a multiple of 32 in [32, 4096]: catalog rows per K9 scan workgroup
+                                      and keys per selection slice (tests: a small catalog spans several chunks) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
@@ -310,6 +313,65 @@ int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets,
 /* score of n (a_i, b_i) pairs, same formula (the reference's `_fingerprint_similarity`) */
 int aid_dedup_pairs(aid_engine *e, const uint32_t *a, const int64_t *a_off, const uint32_t *b, const int64_t *b_off,
                     int32_t n, double *sim);
+
+/* ---- vector ("vibe") lane (spec/FPSPEC.md 9) ----
+ * Replaces the Qdrant collection of app/audio/qdrant_setup.py:50-64 and its search (app/search/vibe.py:164-218,
+ * HNSW over int8-quantised vectors) by an exact brute-force scan of a device-resident catalog of chunk embeddings
+ * (K9, csrc/vector.hip), and app/search/aggregation.py:63-138 by a kernel. The embedding model stays with the
+ * caller: vectors arrive as floats, [n][dim] row-major, and are normalised on the way in (cosine distance).
+ * Scores, hit lists and aggregated rows are the pinned arithmetic of FPSPEC 9, bit for bit.
+ * An entry is one chunk of a track; entry index = insertion order. `tracks` are caller-chosen ids
+ * (AID_VEC_NO_TRACK is reserved). Arrays are host (AID_PCM_HOST) or device (AID_PCM_DEVICE) where a `location`
+ * is given, host otherwise. `stream` as everywhere; every call has finished when it returns. */
+/* Empty the catalog and set its dimension: a multiple of 32 in [32, 1024] (the reference's is 512). */
+int aid_vec_reset(aid_engine *e, int32_t dim);
+/* Append n entries (replaces upsert_track_embeddings' points). chunk_index NULL = 0 .. n-1. The catalog grows on
+   demand. */
+int aid_vec_add(aid_engine *e, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index,
+                const double *offset_sec, int64_t n, int32_t location);
+/* Tombstone every entry of a track (delete_track_embeddings); AID_ERR_INVALID if it has no live entry. */
+int aid_vec_remove(aid_engine *e, uint32_t track);
+/* Drop the tombstoned entries; the others keep their order and are renumbered. *n_removed = entries dropped. */
+int aid_vec_compact(aid_engine *e, int64_t *n_removed);
+int aid_vec_count(aid_engine *e, int64_t *n_entries, int64_t *n_live, int32_t *dim);
+
+typedef struct aid_vec_hit {
+    uint32_t entry;
+    uint32_t track;
+    int32_t chunk_index;
+    float score;
+    double offset_sec;
+} aid_vec_hit;
+/* The `limit` (1..1024) live entries of the largest score per query, score descending then entry ascending
+   (replaces _query_qdrant). hits: host [nq][limit]; n_hits: host [nq]. */
+int aid_vec_search(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                   aid_vec_hit *hits, int32_t *n_hits, void *stream);
+/* Debug and parity view: the whole score matrix [nq][n_entries] to host `out` (capacity `cap` floats); removed
+   entries are included. */
+int aid_vec_scores(aid_engine *e, const float *queries, int32_t nq, int32_t location, float *out, int64_t cap);
+
+typedef struct aid_vibe_row {
+    uint32_t track;
+    int32_t chunk_count; /* hits of the track in the list */
+    double final_score, base_score, diversity_bonus;
+} aid_vibe_row;
+#define AID_VEC_NO_TRACK 0xFFFFFFFFu
+/* aggregate_chunk_hits over nq host hit lists (list q = hits[hoff[q] .. hoff[q+1]), at most 1024 hits each; only
+   track, score and offset_sec are read), then final_score >= threshold and the first max_out. exclude: NULL, or
+   per query a track to drop (AID_VEC_NO_TRACK = none). out: host [nq][max_out]; n_out: host [nq]. */
+int aid_vec_aggregate(aid_engine *e, const aid_vec_hit *hits, const int64_t *hoff, int32_t nq, int32_t top_k_per_track,
+                      double diversity_weight, const uint32_t *exclude, double threshold, int32_t max_out,
+                      aid_vibe_row *out, int32_t *n_out);
+/* Search, aggregation, threshold and limit of a batch of queries in one critical section (run_vibe_lane's steps 2
+   and 3, vibe.py:36-161, without the metadata lookup): safe to call from several threads, like aid_exact_lane. */
+int aid_vibe_lane(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                  int32_t top_k_per_track, double diversity_weight, const uint32_t *exclude, double threshold,
+                  int32_t max_out, aid_vibe_row *out, int32_t *n_out, void *stream);
+/* Flat versioned file (magic AIDFPVC1, u32 version, i32 dim, i64 n, then the normalised vectors as stored, tracks,
+   chunk indices, offsets, tombstones): replaces Qdrant's own persistence. A truncated or foreign file gives
+   AID_ERR_INVALID and leaves the catalog as it was. */
+int aid_vec_save(aid_engine *e, const char *path);
+int aid_vec_load(aid_engine *e, const char *path);
 
 /* ---- native multi-GPU exchange (SURVEY.md 8b "aid_allgather_index", 8e) ----
  * One process per GPU. Rank 0 calls aid_comm_id, the host hands the 128 id bytes to every
