@@ -1,6 +1,7 @@
 // aidfp_vector.h -- the vector lane's catalog (spec/FPSPEC.md 9, K9): host state and entry points of
-// csrc/vector.hip. engine.cpp owns one VecCatalog per engine and calls these under the engine lock with the
-// engine's device current; every function returns AID_OK or an AID_ERR_* code and leaves its message in `err`.
+// csrc/vector.hip. struct aid_engine (engine_internal.h) owns one VecCatalog; engine.cpp calls these under the
+// engine lock with the engine's device current; every function returns AID_OK or an AID_ERR_* code and leaves its
+// message in `err`.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -14,6 +14,7 @@
 // flight score the SAME catalog chunk for different queries and share it through L2; one wave
 // per entry (coalesced 256-B reads, popcount, wave reduction).
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

@@ -3,7 +3,8 @@
 // Owns one GPU's tables and workspaces, builds the per-call clip descriptors
 // (one small H2D copy), launches K1..K3 on the caller's stream and exposes the
 // results. Replaces the `olaf_c` process boundary of the reference
-// (audio-ident-service/app/audio/fingerprint.py:87-270).
+// (audio-ident-service/app/audio/fingerprint.py:87-270). The query half (K5, the query entry points, the exact
+// lane) is query.cpp; engine_internal.h holds what the two files share.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -17,81 +18,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/aidfp.h"
-#include "aidfp_device.h"
-#include "aidfp_layout.h"
-#include "aidfp_vector.h"
+#include "engine_internal.h"
 #include "resample_design.h"
-
-namespace aid {
-void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_frames,
-                       int64_t total_strips, int64_t slots, int hop, const Tables *tab, float *out, bool logmag,
-                       uint64_t *hot, float thr, bool keep_power, uint32_t *qmax, hipStream_t s);
-int peak_pick_blocks_per_cu(int width);
-void launch_peak_pick(int width, const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
-                      int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
-                      const uint32_t *clip_qmax, float rel, hipStream_t s);
-void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
-                      int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
-                      uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips, bool one_chunk_each,
-                      hipStream_t s);
-void launch_synth(float *out, const uint32_t *tracks, const int64_t *starts, int n_clips, int64_t n, int sr,
-                  int noise_a, uint32_t salt, int fmax_hz, bool envelope, const int16_t *sin_tab, hipStream_t s);
-int64_t resample_lds_floats(int up, int down, int J);
-void launch_resample(const void *src, bool s16, int64_t in_base, int64_t n, int channels, int up, int down, int hl,
-                     int J, const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s,
-                     int n_streams = 1, int64_t src_stride = 0, int64_t dst_stride = 0, const void *hist = nullptr,
-                     int64_t hist_n = 0, int64_t hist_stride = 0);
-void launch_s16_to_f32(const int16_t *src, int64_t n, float *dst, hipStream_t s);
-int dedup_chunks(int64_t n_cat);
-void launch_dedup_scan(const uint32_t *cw, const int64_t *coff, const double *cdur, int64_t n_cat, const uint32_t *qw,
-                       const int64_t *qoff, const double *qlo, const double *qhi, int nq, double *part_sim,
-                       int64_t *part_idx, double *best_sim, int64_t *best_idx, hipStream_t s);
-void launch_dedup_pairs(const uint32_t *aw, const int64_t *aoff, const uint32_t *bw, const int64_t *boff, int n,
-                        double *sim, hipStream_t s);
-void launch_index_count(const uint32_t *ph, const uint32_t *ptrack, int64_t n, const uint8_t *tomb, uint32_t n_tracks,
-                        uint32_t *cnt, hipStream_t s);
-void launch_index_scatter(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n,
-                          const uint8_t *tomb, uint32_t n_tracks, uint32_t *cursor, uint64_t *post, hipStream_t s);
-void launch_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t s);
-size_t index_sort_temp_bytes(int64_t n);
-bool k4_ab_sort_built();
-int match_lds_blocks_per_cu();
-size_t radix_scratch_u32(int64_t n);
-hipError_t launch_index_sort_build(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n,
-                                   const uint8_t *tomb, uint32_t n_tracks, uint32_t *keys0, uint32_t *keys1,
-                                   uint64_t *vals0, uint64_t *vals1, void *temp, size_t temp_bytes, bool use_rocprim,
-                                   uint32_t *scratch, uint32_t *E, uint32_t *offsets, unsigned long long *nz,
-                                   uint64_t **vals_out, uint16_t *sig, int rank_mode, hipStream_t s);
-void launch_make_sig(const uint64_t *post, int64_t n, uint16_t *sig, hipStream_t s);
-void launch_compact(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n, const uint8_t *tomb,
-                    uint32_t n_tracks, uint32_t *cnt, uint32_t *off, uint32_t *tmp, uint32_t *oh, uint32_t *otrack,
-                    uint32_t *ot, hipStream_t s);
-void launch_records_to_postings(const uint64_t *recs, const int64_t *src_off, const int64_t *counts,
-                                const int64_t *dst_off, const uint32_t *track_ids, int n_clips, uint32_t *ph,
-                                uint32_t *ptrack, uint32_t *pt, hipStream_t s);
-void launch_append_offsets(const int64_t *counts, int n_clips, int64_t base, int64_t *dst_off, int64_t *total,
-                           hipStream_t s);
-void launch_query_votes(const uint64_t *recs, const int64_t *qstart, const int64_t *qcount, int nq,
-                        const uint32_t *offsets, int64_t *votes, uint64_t *ranges, hipStream_t s);
-void launch_query(const uint64_t *recs, const int64_t *qstart, const int64_t *qcount, int nq, const uint32_t *offsets,
-                  const uint64_t *post, const uint8_t *tomb, uint32_t n_tracks, int min_match, int max_rows,
-                  uint32_t *hist, int hist_bits, uint32_t *hot, int32_t *rows, int32_t *nrows, int tomb_live,
-                  int parts, int stage, uint32_t *dset, int dset_bits, hipStream_t s);
-void launch_count_nonzero(const uint32_t *cnt, int64_t n, unsigned long long *out, hipStream_t s);
-void launch_index_checksum(const uint32_t *ph, const uint32_t *ptr, const uint32_t *pt, int64_t first, int64_t n,
-                           unsigned long long *out, hipStream_t s);
-void launch_match_lds(const uint64_t *recs, const int64_t *qstart, const int64_t *qcount, int nq,
-                      const uint32_t *offsets, const uint64_t *post, const uint8_t *tomb, uint32_t n_tracks,
-                      int min_match, int max_rows, int32_t *rows, int32_t *nrows, int tomb_live, const int64_t *votes,
-                      const uint16_t *sig, const uint64_t *ranges, hipStream_t s);
-uint32_t index_keys();
-void launch_downmix(const float *in, int64_t n, float *out, hipStream_t s);
-void launch_window_gather(const void *src, bool s16, const int64_t *win, int n_win, int64_t max_len, float *dst, hipStream_t s);
-void launch_exact_consensus(const int32_t *rows, const int32_t *nrows, int mr, const int32_t *clip_win, int n_clips,
-                            double sec, int max_out, void *out, int32_t *n_out, hipStream_t s);
-void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
-}  // namespace aid
 
 #if defined(AID_K2_STAMPS)
 namespace aid {
@@ -102,270 +30,14 @@ extern "C" int aid_diag_k2_stamps(unsigned long long *out, int reset) {  // diag
 }
 #endif
 
-using namespace aid;
 
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string &msg) {
+int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(_e == hipErrorOutOfMemory ? AID_ERR_NOMEM : AID_ERR_DEVICE,                \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                        \
-    } while (0)
-
-namespace {
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;  // capacity in elements
-    hipError_t reserve(size_t want) {
-        if (want <= n) return hipSuccess;
-        if (p) {  // growing: in-flight work of earlier calls may still use the old buffer
-            (void)hipDeviceSynchronize();
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        n = 0;
-        size_t cap = std::max(want, (size_t)1);
-        hipError_t e = hipMalloc(&p, cap * sizeof(T));
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// page-locked host buffer (hipHostMalloc): device-to-host copies into it are asynchronous, so a call can queue its
-// result copies behind its kernels and wait once
-template <typename T>
-struct HostBuf {
-    T *p = nullptr;
-    size_t n = 0;  // capacity in elements
-    hipError_t reserve(size_t want) {  // callers have synchronised any copy still targeting the old buffer
-        if (want <= n) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t cap = std::max(want, (size_t)64);
-        hipError_t e = hipHostMalloc((void **)&p, cap * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct ProfEvent {
-    int kernel;
-    hipEvent_t a, b;
-};
-
-}  // namespace
-
-struct aid_engine;
-static void free_ticket_pool(aid_engine *e);
-
-struct aid_engine {
-    aid_config cfg{};
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    Tables *d_tab = nullptr;
-    int16_t *d_sin = nullptr;
-
-    DevBuf<float> pcm_stage;
-    DevBuf<float> power;
-    DevBuf<uint64_t> mask;
-    DevBuf<uint64_t> hotw;  // K1 -> K2: per power row, bit hot_bit(c) = 16-bin chunk c has a value > thr
-    // FPSPEC 5.1 (cfg.peak_rel > 0): per clip of the call, the bit pattern of max Q over its plane. Zeroed on the
-    // call's stream before the first K1, raised by K1's atomics, read by K2 and aid_result_thresholds
-    DevBuf<uint32_t> clip_qmax;
-    DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3
-    // pinned, host-mapped, two words: K3 stores (cold waves | waves << 32) and (twice-walked strips | strips << 32) of
-    // the last K2 here; waves / strips is the width that K2 ran at
-    uint64_t *h_cold = nullptr;
-    uint64_t *h_cold_dev = nullptr;  // its device address
-    int k2_width_force = 0;          // aid_engine_force K2_WIDTH: 2 or 4 quarter waves per K2 workgroup; 0 = adaptive
-    int k2_width = 4;                // the adaptive choice (extract_locked); also the width of the last call
-    int k2_hold = 0;                 // calls left at width 4 after a fall-back from width 2 (hysteresis)
-    double k2_slots_x = 0.0;         // aid_engine_force K2_STRIPS: fixed strips per slot; 0 = adaptive (extract_locked)
-    DevBuf<ClipDesc> desc;
-    DevBuf<int64_t> chunk_counts;
-    DevBuf<uint64_t> records;
-    DevBuf<int64_t> counts;
-    DevBuf<uint32_t> synth_tracks;
-    DevBuf<int64_t> synth_starts;
-    uint8_t *h_synth = nullptr;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
-    size_t h_synth_cap = 0;
-    hipEvent_t synth_ev = nullptr;
-    bool synth_ev_live = false;
-
-    // index (FPSPEC 7): all postings (SoA source of truth) + the CSR built from them
-    DevBuf<uint32_t> p_hash, p_track, p_t;
-    int64_t n_post = 0;  // exact unless post_pend: then the last aid_index_add_extracted's count is in flight
-    // aid_index_add_extracted appends without waiting for its clips' counts: K_append scans them on the device and
-    // the new total comes back to pinned h_npost behind add_ev; settle_postings() makes n_post exact again
-    DevBuf<int64_t> d_npost;
-    int64_t *h_npost = nullptr;
-    hipEvent_t add_ev = nullptr;  // after the last append's staging copies (and, if post_pend, its count copy)
-    bool add_live = false, post_pend = false;
-    std::vector<uint8_t> h_tomb;  // per track id: 1 = removed
-    DevBuf<uint8_t> tomb;
-    uint32_t n_tracks = 0;        // max track id + 1
-    DevBuf<uint32_t> idx_cnt, idx_off, scan_tmp;
-    DevBuf<uint64_t> idx_post;
-    DevBuf<uint16_t> idx_sig;  // K5's 2-B vote signature per CSR posting (aidfp_layout.h posting_sig)
-    DevBuf<uint32_t> srt_k0, srt_k1;  // K4 sort build: key double buffer
-    DevBuf<uint64_t> srt_v;           // K4 sort build: the value buffer idx_post pairs with
-    DevBuf<uint8_t> srt_tmp;          // K4 rocPRIM build (A/B): its temporary storage
-    DevBuf<uint32_t> srt_scratch;     // K4 radix build: per-tile digit counts, their scan, scan temporary
-    int k4_mode = 2;                  // internal K4 build: 2 radix sort (the default; K4_BUILD force 0, 1 or 4),
-                                      // 1 rocPRIM sort (force 3, variant build only), 0 atomic counting sort (force 2)
-    int k4_rank = 0;                  // radix sort's in-wave rank: 0 one LDS atomic per posting where the device
-                                      // serves same-address lanes in order (else ballots), 1 ballots (K4_BUILD 4)
-    bool index_built = false, index_dirty = true;
-    int64_t n_indexed = 0;
-    int64_t n_buckets_used = 0;
-    int64_t n_fallback = 0;  // queries answered by the global-histogram path
-    DevBuf<unsigned long long> nz;
-    DevBuf<unsigned long long> chk;  // aid_index_checksum result
-    // query workspaces
-    DevBuf<uint64_t> q_recs;
-    DevBuf<int64_t> q_start, q_count;
-    DevBuf<uint32_t> q_hist;
-    DevBuf<int32_t> q_rows, q_nrows;
-    DevBuf<uint32_t> q_hot;  // K5h hot-bucket bitmaps, [batch][2^bits / 32]
-    DevBuf<uint32_t> q_dset;  // K5b retries: HBM distinct (slot, t_q) sets, [batch][2^dbits]
-    DevBuf<uint64_t> q_ranges;  // K5: per query record its CSR range (k_query_votes -> k_match_lds)
-    HostBuf<int64_t> hq_meta;   // run_queries: per query start, record count, exact votes (pinned: async D2H)
-    HostBuf<int32_t> hq_n;      // run_queries: the LDS path's per-query row counts
-    HostBuf<int32_t> hq_rows;   // run_queries: the LDS path's rows, [nq][max_results][5]
-    HostBuf<int64_t> hq_start;  // the queries' record starts (clip_base) staged page-locked for their upload
-    std::vector<aid_query_ticket *> ticket_pool;  // collected tickets, reused: their buffers and event stay allocated
-    DevBuf<int64_t> q_votes;  // exact votes per query (LDS-histogram eligibility)
-    DevBuf<int64_t> x_src, x_dst;
-    // batched exact lane (aid_exact_lane): PCM staging, window descriptors, consensus output
-    DevBuf<float> x_in, x_win;
-    DevBuf<int64_t> x_wdesc;
-    DevBuf<int32_t> x_order, x_clipwin, x_nout;
-    DevBuf<double> x_out;  // aid_exact_row, 3 x 8 bytes each
-    DevBuf<int64_t> g_meta;            // all-gather: (count, n_tracks) per rank
-    std::map<std::pair<int32_t, int32_t>, float *> rs_taps;  // (up, down) -> device [up][J] taps
-    // Chromaprint dedup catalog (insertion order) + scan scratch
-    DevBuf<uint32_t> dd_words;
-    DevBuf<int64_t> dd_off;
-    DevBuf<double> dd_dur;
-    int64_t dd_n = 0, dd_nw = 0;
-    DevBuf<uint32_t> dq_words, dq_words2;
-    DevBuf<int64_t> dq_off, dq_off2, dq_idx, dq_pidx;
-    DevBuf<double> dq_lo, dq_hi, dq_sim, dq_psim;
-    VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
-    DevBuf<uint32_t> g_send, g_recv;   // all-gather: [3][max] SoA planes per rank
-    DevBuf<uint32_t> x_tracks;
-    size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
-
-    int64_t *h_stage = nullptr;  // pinned staging of aid_index_add_extracted
-    size_t h_stage_cap = 0;
-    ClipDesc *h_desc = nullptr;  // pinned
-    size_t h_desc_cap = 0;
-    // extraction call hazards, tracked with events instead of a stream sync per call:
-    // h_desc is the source of an async H2D copy; pcm_stage is read by K1
-    hipEvent_t desc_ev = nullptr, stage_ev = nullptr;
-    bool desc_ev_live = false, stage_ev_live = false;
-    hipStream_t stage_stream = nullptr;  // the stream whose K1 read pcm_stage last
-    std::vector<int64_t> desc_key;  // offsets (+ pcm location) the device descriptors were built for
-    ClipDesc *desc_dev_for_key = nullptr;
-    std::vector<int64_t> clip_base;  // host copy of desc[c].hash_base
-    std::vector<int64_t> clip_frames;
-    int n_clips = 0;
-    int64_t total_frames = 0, total_strips = 0, total_chunks = 0, total_records = 0;
-    int64_t k2_slots[2] = {1, 1};  // resident K2 workgroups on the device (CUs x blocks per CU) at width 2, 4
-    int64_t k1_slots = 1;  // resident K1 waves (CUs x kStftWaves: one K1 workgroup per CU)
-    int k5_path = 0;       // aid_engine_force K5_PATH: 0 auto, 1 LDS fast path first, 2 global path only (tests)
-    int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
-    int lane_gather = 0;           // aid_engine_force LANE_GATHER: stage the exact lane's sub-windows (A/B)
-    int64_t plane_rows = 0;        // aid_engine_force PLANE_ROWS: power rows per K1 -> K2 clip group (0 = kPlaneRows)
-    int inject_exchange_fail = 0;  // aid_engine_force EXCHANGE_FAIL: the next exchange's prepare step fails (tests)
-    // aid_match_stats: queries, exact votes, and the postings K5 read (a vote = one 8-B posting per pass)
-    int64_t st_queries = 0, st_votes = 0, st_post_reads = 0, st_q_global = 0, st_q_lds = 0, st_records = 0;
-    int64_t st_sig_reads = 0;  // 2-B posting signatures the LDS path read (two per vote: counting and insert passes)
-    int64_t st_fb_reason[5] = {0, 0, 0, 0, 0};  // LDS-path fallbacks (speculative pass) by reason (index.hip)
-    int64_t tomb_since_build = 0;  // removals after the last CSR build (queries must check tomb[])
-    size_t k5_batch = 2048;        // global-path queries per launch
-    hipStream_t last_stream = nullptr;
-    bool have_result = false;
-
-    bool profiling = false;
-    uint32_t prof_mask = 0xFFFFFFFFu;  // bit k: kernel id k gets events (aid_profile_select)
-    std::vector<ProfEvent> pending;
-    std::vector<hipEvent_t> pool;
-    double prof_ms[AID_K_COUNT] = {};
-    int64_t prof_n[AID_K_COUNT] = {};
-    std::mutex mu;
-};
-
-static hipEvent_t take_event(aid_engine *e) {
-    if (!e->pool.empty()) {
-        hipEvent_t ev = e->pool.back();
-        e->pool.pop_back();
-        return ev;
-    }
-    hipEvent_t ev = nullptr;
-    if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-    return ev;
-}
-
-// attached = the scope wraps exactly one timed_launch: its events are stamped by the dispatch itself
-// (aidfp_device.h LaunchTiming); otherwise two hipEventRecord markers bracket the scope.
-struct ProfScope {
-    aid_engine *e;
-    int k;
-    hipStream_t s;
-    bool attached;
-    hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(aid_engine *e_, int k_, hipStream_t s_, bool attached_ = false) : e(e_), k(k_), s(s_), attached(attached_) {
-        if (!e->profiling || !((e->prof_mask >> k) & 1u) || !(a = take_event(e))) return;
-        if (!attached) {
-            (void)hipEventRecord(a, s);
-            return;
-        }
-        if (!(b = take_event(e))) {
-            e->pool.push_back(a);
-            a = nullptr;
-            return;
-        }
-        launch_timing().start = a;
-        launch_timing().stop = b;
-    }
-    ~ProfScope() {
-        if (!a) return;
-        if (attached) {
-            LaunchTiming &t = launch_timing();
-            if (t.start) {  // nothing was launched: the events were never stamped
-                t.start = t.stop = nullptr;
-                e->pool.push_back(a);
-                e->pool.push_back(b);
-                return;
-            }
-        } else {
-            if (!(b = take_event(e))) return;
-            (void)hipEventRecord(b, s);
-        }
-        e->pending.push_back({k, a, b});
-    }
-};
 
 static void build_tables(Tables &t) {
     auto tw = [](int j, int L) {
@@ -379,19 +51,6 @@ static void build_tables(Tables &t) {
     for (int j = 0; j < 64; ++j) t.t64[j] = tw(j, 64);
     for (int j = 0; j < 1024; ++j) t.t1k[j] = tw(j, 1024);
     for (int j = 0; j < 1024; ++j) t.t2k[j] = tw(j, 2048);
-}
-
-static hipStream_t pick_stream(aid_engine *e, void *stream) {
-    return stream ? (hipStream_t)stream : e->own_stream;
-}
-
-// A host-PCM call copies the caller's samples with ONE hipMemcpyAsync on the call's stream; from page-locked
-// memory that copy is a real DMA that can still be running when the call returns. On success the caller syncs
-// before reusing its buffer (include/aidfp.h); on an error return the engine drains the stream itself, so a
-// caller that reuses or frees its buffer after a failed call cannot race the copy. Returns rc.
-static int drain_host_copy(aid_engine *e, int32_t loc, void *stream, int rc) {
-    if (rc != AID_OK && loc == AID_PCM_HOST && e) (void)hipStreamSynchronize(pick_stream(e, stream));
-    return rc;
 }
 
 extern "C" {
@@ -539,9 +198,7 @@ void aid_engine_destroy(aid_engine *e) {
     e->q_hot.release();
     e->q_dset.release();
     e->q_ranges.release();
-    e->hq_meta.release();
-    e->hq_n.release();
-    e->hq_rows.release();
+    e->k5h.release();
     e->hq_start.release();
     free_ticket_pool(e);
     e->q_rows.release();
@@ -602,7 +259,7 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
     std::lock_guard<std::mutex> lk(e->mu);
     switch (what) {
         case AID_FORCE_K5_PATH:
-            if (value < 0 || value > 2) return fail(AID_ERR_INVALID, "K5_PATH: 0 auto, 1 LDS first, 2 global");
+            if (value < 0 || value > 2) return fail(AID_ERR_INVALID, "K5_PATH: 0 auto, 1 as 0, 2 global");
             e->k5_path = value;
             return AID_OK;
         case AID_FORCE_K5_PARTS:
@@ -662,32 +319,9 @@ int64_t aid_num_frames(const aid_engine *e, int64_t n) { return e ? num_frames(n
 
 int64_t aid_hash_capacity(const aid_engine *e, int64_t n) { return e ? hash_capacity(num_frames(n, e->cfg.hop)) : 0; }
 
-// PCM sample format of an entry point (FPSPEC 8). The float functions and their _s16 twins funnel into one
-// implementation each, which takes the samples as const void * plus the format; offsets count samples either way
-enum PcmFmt : int { kF32 = 0, kS16 = 1 };
-static inline size_t pcm_size(PcmFmt f) { return f == kS16 ? sizeof(int16_t) : sizeof(float); }
-static inline const void *pcm_at(const void *p, PcmFmt f, int64_t i) {
-    return static_cast<const char *>(p) + i * (int64_t)pcm_size(f);
-}
-
-static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                          int32_t loc, void *stream, const int64_t *ends = nullptr);
-
 // power rows per K1 -> K2 clip group of one extraction call (3 GB of plane; extract_locked)
 constexpr int64_t kPlaneRows = (int64_t)3 << 18;
 
-// the argument checks every clip-batch entry point shares (fn = its name, for the message)
-static int check_clips(const char *fn, aid_engine *e, const void *pcm, const int64_t *offsets, int32_t n_clips,
-                       int32_t loc) {
-    const std::string f(fn);
-    if (!e || !offsets || n_clips < 0) return fail(AID_ERR_INVALID, f + ": bad argument");
-    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, f + ": bad pcm_location");
-    for (int c = 0; c < n_clips; ++c)
-        if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
-            return fail(AID_ERR_INVALID, f + ": offsets must be non-decreasing and >= 0");
-    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, f + ": null pcm");
-    return AID_OK;
-}
 
 static int extract_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
                          int32_t n_clips, int32_t loc, void *stream) {
@@ -707,8 +341,8 @@ int aid_extract_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, i
 
 // Clip c is pcm[offsets[c], offsets[c + 1]); with `ends` (device PCM only) it is pcm[offsets[c], ends[c]), so
 // clips may overlap (the exact lane's sub-windows are read in place).
-static int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                          int32_t loc, void *stream, const int64_t *ends) {
+int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                   void *stream, const int64_t *ends) {
     if (ends && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "extract: clip ends need device PCM");
     HIP_TRY(hipSetDevice(e->device));
     auto clip_len = [&](int c) { return (ends ? ends[c] : offsets[c + 1]) - offsets[c]; };
@@ -1537,7 +1171,7 @@ int aid_profile_read(aid_engine *e, double *ms, int64_t *launches, int32_t reset
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- index + query
+// ---------------------------------------------------------------- index
 
 static int grow_copy_u32(DevBuf<uint32_t> &b, size_t keep, size_t want, hipStream_t s) {
     if (want <= b.n) return AID_OK;
@@ -1856,10 +1490,7 @@ static int finalize_locked(aid_engine *e) {
     HIP_TRY(hipGetLastError());
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, e->idx_off.p + (K - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    unsigned long long used = 0;
-    HIP_TRY(hipMemcpyAsync(&used, e->nz.p, sizeof(used), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    e->n_buckets_used = (int64_t)used;
     e->n_indexed = total;
     e->index_built = true;
     e->index_dirty = false;
@@ -1873,6 +1504,11 @@ static int finalize_locked(aid_engine *e) {
         e->srt_tmp.release();
         e->srt_scratch.release();
     }
+    return AID_OK;
+}
+
+int ensure_index(aid_engine *e) {
+    if (e->index_dirty || !e->index_built) return finalize_locked(e);
     return AID_OK;
 }
 
@@ -2330,555 +1966,6 @@ int aid_index_load(aid_engine *e, const char *path) {
     return AID_OK;
 }
 
-constexpr double kForwardedPerBucket = 2.0;  // forwarded votes (1-bit filter estimate) per global histogram bucket
-// run K5 over nq queries whose records are at device ranges (q_start/q_count device arrays).
-// Exact per-query vote counts (k_query_votes) choose the path and size the vote histogram;
-// queries whose exact LDS table overflowed are re-run with 4x the buckets. rec_cap: elements of `recs` (the per-record
-// CSR range cache the vote count writes for the LDS path has one entry per record index).
-// rows == nullptr: device mode, every query's rows end in e->q_rows ([nq][max_results][5] int32);
-// nrows (host) is always filled
-
-static int run_queries(aid_engine *e, const uint64_t *recs, const int64_t *qstart_dev, const int64_t *qcount_dev,
-                       int nq, int64_t rec_cap, aid_match_row *rows, int32_t *nrows, hipStream_t s) {
-    const int mr = e->cfg.max_results;
-    HIP_TRY(e->q_rows.reserve((size_t)std::max(nq, 1) * mr * 5));
-    HIP_TRY(e->q_nrows.reserve((size_t)std::max(nq, 1)));
-    std::vector<int> todo(nq);
-    for (int q = 0; q < nq; ++q) todo[q] = q;
-    std::vector<int64_t> h_start(nq), h_count(nq), h_votes(nq, 0);
-    // the per-query metadata and (below) the LDS path's rows come back through page-locked buffers: the copies are
-    // queued behind the kernels and the call waits ONCE (a pageable destination made each copy a host wait, so K5
-    // was launched only after a round trip behind the extraction)
-    HIP_TRY(e->hq_meta.reserve((size_t)3 * nq));
-    int64_t *p_start = e->hq_meta.p, *p_count = p_start + nq, *p_votes = p_count + nq;
-    HIP_TRY(hipMemcpyAsync(p_start, qstart_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(p_count, qcount_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    {  // exact vote counts: path choice and the global histogram's size
-        HIP_TRY(e->q_votes.reserve((size_t)nq));
-        const bool ranges = e->k5_path == 0 || e->k5_path == 1;  // the LDS path reads them
-        if (ranges) HIP_TRY(e->q_ranges.reserve((size_t)std::max<int64_t>(rec_cap, 1)));
-        launch_query_votes(recs, qstart_dev, qcount_dev, nq, e->idx_off.p, e->q_votes.p, ranges ? e->q_ranges.p : nullptr,
-                           s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(p_votes, e->q_votes.p, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
-    // the LDS path is launched right away, in the same round trip as the vote counts instead of after them (one
-    // host sync less per call). It routes each query by its own count (K5 reads q_votes on the device): a query
-    // above kLdsMaxVotes is handed back (nrows -1) without an LDS run, and one that overflows its counters reports
-    // -1 too; both fall through to the global path below. Round 2 did this for batches of <= 16 queries, gated on
-    // the previous batch's heaviest query, because the LDS kernel then ran heavy queries too; with per-query
-    // routing (round 5) a batch of any size takes it, the coalesced service batches and the stream pushes included
-    const bool speculate = e->k5_path == 0;
-    std::vector<int32_t> spec_n;
-    if (speculate) {
-        {
-            ProfScope ps(e, AID_K_MATCH, s, true);
-            launch_match_lds(recs, qstart_dev, qcount_dev, nq, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                             e->cfg.min_match, mr, e->q_rows.p, e->q_nrows.p, e->tomb_since_build > 0, e->q_votes.p,
-                             e->idx_sig.p, e->q_ranges.p, s);
-        }
-        HIP_TRY(hipGetLastError());
-        spec_n.resize(nq);
-        if (rows) {
-            HIP_TRY(e->hq_rows.reserve((size_t)nq * mr * 5));
-            HIP_TRY(hipMemcpyAsync(e->hq_rows.p, e->q_rows.p, (size_t)nq * mr * sizeof(aid_match_row),
-                                   hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(e->hq_n.reserve((size_t)nq));
-        HIP_TRY(hipMemcpyAsync(e->hq_n.p, e->q_nrows.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(h_start.data(), p_start, nq * sizeof(int64_t));
-    std::memcpy(h_count.data(), p_count, nq * sizeof(int64_t));
-    std::memcpy(h_votes.data(), p_votes, nq * sizeof(int64_t));
-    if (speculate) {
-        std::memcpy(spec_n.data(), e->hq_n.p, nq * sizeof(int32_t));
-        if (rows) std::memcpy(rows, e->hq_rows.p, (size_t)nq * mr * sizeof(aid_match_row));
-        std::vector<int> again;
-        for (int q = 0; q < nq; ++q) {
-            if (spec_n[q] < 0) {
-                again.push_back(q);
-                ++e->st_fb_reason[std::min(-spec_n[q], 5) - 1];
-            } else {
-                nrows[q] = spec_n[q];
-            }
-        }
-        todo.swap(again);
-        e->n_fallback += (int64_t)todo.size();
-    }
-    int64_t vmax = 1;
-    for (int q = 0; q < nq; ++q) vmax = std::max(vmax, h_votes[q]);
-    const double votes = (double)vmax;
-    e->st_queries += nq;
-    for (int q = 0; q < nq; ++q) {
-        e->st_votes += h_votes[q];
-        e->st_records += h_count[q];
-    }
-    if (speculate)  // the LDS path ran every light query once: two enumerations (counting, then the exact inserts)
-        for (int q = 0; q < nq; ++q) e->st_sig_reads += h_votes[q] <= kLdsMaxVotes ? 2 * h_votes[q] : 0;
-    // global histogram, sized for the votes that pass K5a's 2^20-bit seen filter (all but the
-    // distinct bits: v - m(1 - e^{-v/m})) at ~2 per bucket: a chance bucket reaching
-    // min_match - 1 then has probability ~1e-5. Sizing it for ALL votes (2 buckets each: 2 MB rows on
-    // config 4) spread K5a's random atomics over ~4 GB of rows, all HBM round trips: 16 bits
-    // (256 KB rows, 64 MB for the 256 resident queries: Infinity-Cache resident) took 0.295 s
-    // against 0.383 s for 19 bits on config 4 (37.3k against 28.8k clips/s; 20 bits: 23.4k).
-    // K5a key partitions (a workgroup and a 2^20-bit seen filter each): two once the filter
-    // saturates (> 2^18 votes; config 4's ~540k: 46.6k -> 60.2k clips/s), else one
-    const int parts = e->k5_parts > 0 ? e->k5_parts : votes > (double)(1 << 18) ? 2 : 1;
-    const double m_seen = (double)(1 << 20), vp = votes / parts;
-    const double fwd = parts * (vp - m_seen * (1.0 - std::exp(-vp / m_seen)));
-    int bits = 15;
-    while (bits < 24 && (double)(1ull << bits) < fwd / kForwardedPerBucket) ++bits;
-    // LDS fast path while its 2^16 counters stay sparse enough. It is exact for heavier queries too (overflows
-    // fall back; tests/test_gpu_match_load.py) but one query per CU cannot keep enough posting reads in flight:
-    // round-1 config 4 (v0 catalog, ~540k votes per window) took 48.6 s on it against 1.43 s on the global path.
-    // On the v2 catalog (~84.5k votes per window, probes/k5_path_probe.py) it is the faster path (201k against
-    // 185k clips/s, rows equal), so a batch goes to it when its mean query has <= 2^17 votes (2 per counter) and
-    // none has more than 2^20 (a heavier one falls back to the global path after its LDS run)
-    // Each query is routed by its own vote count: k_match_lds answers the queries with <= kLdsMaxVotes
-    // (2^18 votes over the 2^16 4-bit counters of its filter = 4 per counter, aidfp_layout.h) and hands heavier ones
-    // straight back (nrows -1, no LDS run), so the batch takes
-    // the LDS launch whenever some query is light enough for it; the heavy ones run on the global path below
-    int n_light = 0;
-    for (int q = 0; q < nq; ++q) n_light += h_votes[q] <= kLdsMaxVotes;
-    const bool fast = !speculate && (e->k5_path == 1 || (e->k5_path == 0 && n_light > 0));
-    // fast path: the whole vote filter in LDS (K5 `k_match_lds`); overflowed queries fall
-    // through to the global-histogram path below
-    if (fast) {
-        {
-            ProfScope ps(e, AID_K_MATCH, s, true);
-            launch_match_lds(recs, qstart_dev, qcount_dev, nq, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                             e->cfg.min_match, mr, e->q_rows.p, e->q_nrows.p, e->tomb_since_build > 0, e->q_votes.p,
-                             e->idx_sig.p, e->q_ranges.p, s);
-        }
-        HIP_TRY(hipGetLastError());
-        std::vector<int32_t> got_n(nq);
-        if (rows)
-            HIP_TRY(hipMemcpyAsync(rows, e->q_rows.p, (size_t)nq * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(got_n.data(), e->q_nrows.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        std::vector<int> again;
-        for (int q = 0; q < nq; ++q) {
-            if (got_n[q] < 0) again.push_back(q);
-            else nrows[q] = got_n[q];
-        }
-        todo.swap(again);
-        e->n_fallback += (int64_t)todo.size();
-        for (int q = 0; q < nq; ++q)  // counting pass + insert pass (2 B each), light queries only
-            e->st_sig_reads += h_votes[q] <= kLdsMaxVotes ? 2 * h_votes[q] : 0;
-        e->st_q_lds += n_light;
-    }
-    if (speculate) e->st_q_lds += n_light;
-    for (int attempt = 1; !todo.empty(); ++attempt, bits += 2) {
-        for (int q : todo) e->st_post_reads += h_votes[q] * (parts + 1);  // K5a once per key partition, K5b once
-        e->st_q_global += (int64_t)todo.size();
-        if (bits > 26) return fail(AID_ERR_STATE, "query vote table overflow (too many candidate votes)");
-        const size_t H = (size_t)1 << bits;
-        const int batch = (int)std::max<size_t>(1, std::min<size_t>(e->k5_batch, ((size_t)4 << 30) / (H * 4)));
-        HIP_TRY(e->q_hist.reserve((size_t)std::min<int>((int)todo.size(), batch) * H));
-        HIP_TRY(e->q_hot.reserve((size_t)std::min<int>((int)todo.size(), batch) * (H / 32)));
-        if (e->hist_zero_cap != e->q_hist.n) {  // fresh allocation; K5h re-zeroes its rows afterwards
-            HIP_TRY(hipMemsetAsync(e->q_hist.p, 0, e->q_hist.n * sizeof(uint32_t), s));
-            e->hist_zero_cap = e->q_hist.n;
-        }
-        const int64_t *qs = qstart_dev, *qc = qcount_dev;
-        int32_t *out_rows = e->q_rows.p, *out_n = e->q_nrows.p;
-        std::vector<int> order = todo;
-        if (attempt > 0) {  // gather the overflowed queries' ranges into the scratch arrays' tail
-            HIP_TRY(e->x_src.reserve(2 * order.size()));
-            std::vector<int64_t> st(order.size()), ct(order.size());
-            for (size_t i = 0; i < order.size(); ++i) { st[i] = h_start[order[i]]; ct[i] = h_count[order[i]]; }
-            HIP_TRY(hipMemcpyAsync(e->x_src.p, st.data(), st.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(e->x_src.p + order.size(), ct.data(), ct.size() * sizeof(int64_t),
-                                   hipMemcpyHostToDevice, s));
-            qs = e->x_src.p;
-            qc = e->x_src.p + order.size();
-            HIP_TRY(e->x_dst.reserve(((size_t)order.size() * mr * 5 + 1) / 2 + order.size()));
-            out_rows = reinterpret_cast<int32_t *>(e->x_dst.p);
-            out_n = out_rows + (size_t)order.size() * mr * 5;
-        }
-        const int n = (int)order.size();
-        // from the second global attempt on, the distinct (slot, t_q) sets live in HBM (2^dbits entries per query,
-        // 4x more per attempt): a query that overflowed k_vote_final's LDS set is a long one with a strong match
-        // (FPSPEC v1 7), which more histogram buckets do not help
-        const int dbits = attempt >= 2 ? std::min(12 + 2 * attempt, 26) : 0;
-        int dbatch = batch;
-        if (dbits) {
-            dbatch = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, ((size_t)1 << 30) / ((size_t)4 << dbits)));
-            HIP_TRY(e->q_dset.reserve((size_t)std::min(dbatch, n) << dbits));
-        }
-        for (int q0 = 0; q0 < n; q0 += dbatch) {
-            const int nb = std::min(dbatch, n - q0);
-            if (dbits) HIP_TRY(hipMemsetAsync(e->q_dset.p, 0xFF, ((size_t)nb << dbits) * sizeof(uint32_t), s));
-            // K5a, K5h, K5b, each with its own dispatch-attached events when profiled
-            for (int stage = 1; stage <= 3; ++stage) {
-                ProfScope ps(e, stage == 1 ? AID_K_VOTE_HIST : stage == 2 ? AID_K_HOT_SCAN : AID_K_VOTE_FINAL, s, true);
-                launch_query(recs, qs + q0, qc + q0, nb, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                             e->cfg.min_match, mr, e->q_hist.p, bits, e->q_hot.p, out_rows + (size_t)q0 * mr * 5,
-                             out_n + q0, e->tomb_since_build > 0, parts, stage, dbits ? e->q_dset.p : nullptr, dbits,
-                             s);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        std::vector<int32_t> got_n(n);
-        std::vector<aid_match_row> got;
-        if (rows) {
-            got.resize((size_t)n * mr);
-            HIP_TRY(hipMemcpyAsync(got.data(), out_rows, (size_t)n * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
-        } else {  // device mode: the batch's rows go to their queries' slots of q_rows
-            HIP_TRY(e->x_order.reserve(order.size()));
-            HIP_TRY(hipMemcpyAsync(e->x_order.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            launch_rows_scatter(out_rows, e->x_order.p, n, mr, e->q_rows.p, s);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(got_n.data(), out_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        std::vector<int> again;
-        for (int i = 0; i < n; ++i) {
-            const int q = order[i];
-            if (got_n[i] < 0) {
-                again.push_back(q);
-                continue;
-            }
-            nrows[q] = got_n[i];
-            if (rows) std::memcpy(rows + (size_t)q * mr, got.data() + (size_t)i * mr, (size_t)mr * sizeof(aid_match_row));
-        }
-        todo.swap(again);
-    }
-    return AID_OK;
-}
-
-// K5 keys its distinct-frame sets by (table slot << 20 | t_q) (index.hip distinct_first): a query's anchor frames must
-// stay below 2^20 - 1 (3.4 h of audio at 44.1 kHz, 4.6 h at 16 kHz)
-constexpr int64_t kMaxQueryFrame = ((int64_t)1 << 20) - 2;
-static int check_query_frames(const aid_engine *e) {
-    for (int c = 0; c < e->n_clips; ++c)
-        if (e->clip_frames[c] > kMaxQueryFrame + 1)
-            return fail(AID_ERR_INVALID, "query clip longer than 2^20 - 1 frames (FPSPEC v1 7)");
-    return AID_OK;
-}
-
-static int ensure_index(aid_engine *e) {
-    if (e->index_dirty || !e->index_built) return finalize_locked(e);
-    return AID_OK;
-}
-
-int aid_query(aid_engine *e, const aid_hash *recs, const int64_t *qoff, int32_t nq, aid_match_row *rows,
-              int32_t *nrows) {
-    if (!e || nq < 0 || !qoff || (nq > 0 && (!rows || !nrows))) return fail(AID_ERR_INVALID, "aid_query: bad argument");
-    if (nq == 0) return AID_OK;
-    for (int q = 0; q < nq; ++q)
-        if (qoff[q + 1] < qoff[q]) return fail(AID_ERR_INVALID, "aid_query: offsets must be non-decreasing");
-    for (int64_t i = qoff[0]; i < qoff[nq]; ++i)
-        if ((int64_t)recs[i].t1 > kMaxQueryFrame)
-            return fail(AID_ERR_INVALID, "aid_query: record anchor frame >= 2^20 - 1 (FPSPEC v1 7)");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = ensure_index(e)) return rc;
-    hipStream_t s = e->own_stream;
-    const int64_t n = qoff[nq] - qoff[0];
-    HIP_TRY(e->q_recs.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_TRY(e->q_start.reserve(nq));
-    HIP_TRY(e->q_count.reserve(nq));
-    std::vector<int64_t> st(nq), ct(nq);
-    for (int q = 0; q < nq; ++q) {
-        st[q] = qoff[q] - qoff[0];
-        ct[q] = qoff[q + 1] - qoff[q];
-    }
-    if (n > 0) HIP_TRY(hipMemcpyAsync(e->q_recs.p, recs + qoff[0], n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->q_start.p, st.data(), nq * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->q_count.p, ct.data(), nq * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    int64_t mx = 0;
-    for (int q = 0; q < nq; ++q) mx = std::max(mx, ct[q]);
-    (void)mx;
-    return run_queries(e, e->q_recs.p, e->q_start.p, e->q_count.p, nq, std::max<int64_t>(n, 1), rows, nrows, s);
-}
-
-// q_start <- clip_base through page-locked staging: from the engine's std::vector (pageable) the copy could hold
-// the host until the stream had drained the extraction queued before it. Every caller waits for its stream before
-// returning, so the staging is free again at the next call.
-static hipError_t upload_clip_base(aid_engine *e, int n, hipStream_t s) {
-    hipError_t he = e->hq_start.reserve((size_t)n);
-    if (he != hipSuccess) return he;
-    std::memcpy(e->hq_start.p, e->clip_base.data(), (size_t)n * sizeof(int64_t));
-    return hipMemcpyAsync(e->q_start.p, e->hq_start.p, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s);
-}
-
-static int query_extracted_locked(aid_engine *e, aid_match_row *rows, int32_t *nrows) {
-    if (int rc = check_query_frames(e)) return rc;
-    if (int rc = ensure_index(e)) return rc;
-    hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
-    const int nq = e->n_clips;
-    if (nq == 0) return AID_OK;
-    if (!rows || !nrows) return fail(AID_ERR_INVALID, "null output");
-    HIP_TRY(e->q_start.reserve(nq));
-    HIP_TRY(upload_clip_base(e, nq, s));
-    return run_queries(e, e->records.p, e->q_start.p, e->counts.p, nq, (int64_t)e->records.n, rows, nrows, s);
-}
-
-int aid_query_extracted(aid_engine *e, aid_match_row *rows, int32_t *nrows) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction to query with");
-    std::lock_guard<std::mutex> lk(e->mu);
-    return query_extracted_locked(e, rows, nrows);
-}
-
-static int query_pcm_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
-                           int32_t n_clips, int32_t loc, aid_match_row *rows, int32_t *nrows, void *stream) {
-    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
-    if (n_clips > 0 && (!rows || !nrows)) return fail(AID_ERR_INVALID, std::string(fn) + ": null output");
-    if (n_clips == 0) return AID_OK;
-    // one critical section: no other thread's extraction can land between this batch's K1-K3 and K5
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = ensure_index(e)) return rc;
-    if (int rc = extract_locked(e, pcm, fmt, offsets, n_clips, loc, stream)) return drain_host_copy(e, loc, stream, rc);
-    return drain_host_copy(e, loc, stream, query_extracted_locked(e, rows, nrows));
-}
-
-int aid_query_pcm(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                  aid_match_row *rows, int32_t *nrows, void *stream) {
-    return query_pcm_entry("aid_query_pcm", e, pcm, kF32, offsets, n_clips, loc, rows, nrows, stream);
-}
-
-int aid_query_pcm_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                      aid_match_row *rows, int32_t *nrows, void *stream) {
-    return query_pcm_entry("aid_query_pcm_s16", e, pcm, kS16, offsets, n_clips, loc, rows, nrows, stream);
-}
-
-// ---- asynchronous windowed query: submit enqueues the extraction, K5's LDS path and the result
-// copies and returns; collect waits for the ticket's event. The ticket owns page-locked result buffers and a device copy
-// of its records (the next submit reuses the engine's extraction buffers in stream order), so a query the LDS path
-// hands back can still be answered on the global path at collect time.
-struct aid_query_ticket {
-    int nq = 0;
-    int64_t nrec = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    HostBuf<int32_t> rows, nrows;
-    HostBuf<int64_t> meta;  // [0, nq) record starts, [nq, 2nq) record counts, [2nq, 3nq) exact votes
-    DevBuf<uint64_t> recs;
-    DevBuf<int64_t> qsc;    // device record starts and counts of the ticket's queries ([0, nq), [nq, 2nq))
-    ~aid_query_ticket() {
-        if (ev) (void)hipEventDestroy(ev);
-        rows.release();
-        nrows.release();
-        meta.release();
-        recs.release();
-        qsc.release();
-    }
-};
-
-static void free_ticket_pool(aid_engine *e) {
-    for (aid_query_ticket *t : e->ticket_pool) delete t;
-    e->ticket_pool.clear();
-}
-
-static aid_query_ticket *take_ticket(aid_engine *e) {
-    // a pooled ticket keeps its page-locked and device buffers and its event: allocating them per call (hipHostMalloc,
-    // hipMalloc, and the hipFree that synchronises the device on release) had cost more than the overlap gained
-    if (e->ticket_pool.empty()) return new aid_query_ticket();
-    aid_query_ticket *t = e->ticket_pool.back();
-    e->ticket_pool.pop_back();
-    return t;
-}
-
-// the body both submit entries share (engine lock held): the extraction of n clips, K5's LDS pass over the ticket's
-// own copy of the records, the result copies into its page-locked buffers and its event
-static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, const int64_t *ends,
-                         int32_t n, int32_t loc, void *stream, aid_query_ticket *t) {
-    t->nq = n;
-    t->nrec = 0;
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = ensure_index(e)) return rc;
-    if (n == 0) return AID_OK;
-    if (int rc = extract_locked(e, pcm, fmt, offsets, n, loc, stream, ends)) return rc;
-    if (int rc = check_query_frames(e)) return rc;
-    hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
-    t->s = s;
-    const int nq = n, mr = e->cfg.max_results;
-    t->nrec = e->clip_base[nq - 1] + hash_capacity(e->clip_frames[nq - 1]);
-    HIP_TRY(t->meta.reserve((size_t)3 * nq));
-    HIP_TRY(t->rows.reserve((size_t)nq * mr * 5));
-    HIP_TRY(t->nrows.reserve((size_t)nq));
-    HIP_TRY(t->recs.reserve((size_t)std::max<int64_t>(t->nrec, 1)));
-    HIP_TRY(t->qsc.reserve((size_t)2 * nq));
-    std::memcpy(t->meta.p, e->clip_base.data(), (size_t)nq * sizeof(int64_t));
-    // the ticket's own copies: record starts (from its page-locked meta), counts and records (device to device)
-    HIP_TRY(hipMemcpyAsync(t->qsc.p, t->meta.p, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t->qsc.p + nq, e->counts.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t->recs.p, e->records.p, (size_t)t->nrec * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t->meta.p + nq, e->counts.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(e->q_votes.reserve((size_t)nq));
-    HIP_TRY(e->q_ranges.reserve((size_t)std::max<int64_t>(t->nrec, 1)));
-    HIP_TRY(e->q_rows.reserve((size_t)nq * mr * 5));
-    HIP_TRY(e->q_nrows.reserve((size_t)nq));
-    launch_query_votes(t->recs.p, t->qsc.p, t->qsc.p + nq, nq, e->idx_off.p, e->q_votes.p, e->q_ranges.p, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(t->meta.p + 2 * nq, e->q_votes.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    {
-        ProfScope ps(e, AID_K_MATCH, s, true);
-        launch_match_lds(t->recs.p, t->qsc.p, t->qsc.p + nq, nq, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                         e->cfg.min_match, mr, e->q_rows.p, e->q_nrows.p, e->tomb_since_build > 0, e->q_votes.p,
-                         e->idx_sig.p, e->q_ranges.p, s);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(t->rows.p, e->q_rows.p, (size_t)nq * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(t->nrows.p, e->q_nrows.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (!t->ev) HIP_TRY(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(t->ev, s));
-    return AID_OK;
-}
-
-static int windows_submit_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *starts,
-                                const int64_t *ends, int32_t n_windows, void *stream, aid_query_ticket **out) {
-    if (!e || n_windows < 0 || !out || (n_windows > 0 && (!starts || !ends || !pcm)))
-        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
-    *out = nullptr;
-    for (int c = 0; c < n_windows; ++c)
-        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, std::string(fn) + ": bad window");
-    std::lock_guard<std::mutex> lk(e->mu);
-    std::unique_ptr<aid_query_ticket> t(take_ticket(e));
-    if (int rc = submit_locked(e, pcm, fmt, starts, ends, n_windows, AID_PCM_DEVICE, stream, t.get())) return rc;
-    *out = t.release();
-    return AID_OK;
-}
-
-extern "C" int aid_query_windows_submit(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends,
-                                        int32_t n_windows, void *stream, aid_query_ticket **out) {
-    return windows_submit_entry("aid_query_windows_submit", e, pcm, kF32, starts, ends, n_windows, stream, out);
-}
-
-extern "C" int aid_query_windows_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts,
-                                            const int64_t *ends, int32_t n_windows, void *stream,
-                                            aid_query_ticket **out) {
-    return windows_submit_entry("aid_query_windows_submit_s16", e, pcm, kS16, starts, ends, n_windows, stream, out);
-}
-
-// aid_query_pcm in two halves (the query coalescer's pipelined batches): host PCM must stay unchanged until the ticket
-// is collected (its one H2D copy is queued, not waited for)
-static int pcm_submit_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
-                            int32_t n_clips, int32_t loc, void *stream, aid_query_ticket **out) {
-    if (!out) return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
-    *out = nullptr;
-    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
-    std::lock_guard<std::mutex> lk(e->mu);
-    std::unique_ptr<aid_query_ticket> t(take_ticket(e));
-    if (int rc = submit_locked(e, pcm, fmt, offsets, nullptr, n_clips, loc, stream, t.get()))
-        return drain_host_copy(e, loc, stream, rc);
-    *out = t.release();
-    return AID_OK;
-}
-
-extern "C" int aid_query_pcm_submit(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips,
-                                    int32_t loc, void *stream, aid_query_ticket **out) {
-    return pcm_submit_entry("aid_query_pcm_submit", e, pcm, kF32, offsets, n_clips, loc, stream, out);
-}
-
-extern "C" int aid_query_pcm_submit_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
-                                        int32_t loc, void *stream, aid_query_ticket **out) {
-    return pcm_submit_entry("aid_query_pcm_submit_s16", e, pcm, kS16, offsets, n_clips, loc, stream, out);
-}
-
-extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid_match_row *rows, int32_t *nrows) {
-    if (!e || !t) {
-        delete t;
-        return fail(AID_ERR_INVALID, "aid_query_windows_collect: bad argument");
-    }
-    if (t->nq > 0 && (!rows || !nrows)) {
-        if (t->ev) (void)hipEventSynchronize(t->ev);
-        std::lock_guard<std::mutex> lk(e->mu);
-        e->ticket_pool.push_back(t);
-        return fail(AID_ERR_INVALID, "aid_query_windows_collect: bad argument");
-    }
-    if (t->nq > 0) {
-        const hipError_t we = hipEventSynchronize(t->ev);
-        if (we != hipSuccess) {
-            delete t;
-            return fail(AID_ERR_DEVICE, std::string("aid_query_windows_collect: ") + hipGetErrorString(we));
-        }
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    struct Back {  // back to the pool on every return below (the ticket's work has completed)
-        aid_engine *e;
-        aid_query_ticket *t;
-        ~Back() { e->ticket_pool.push_back(t); }
-    } back{e, t};
-    if (t->nq == 0) return AID_OK;
-    const int nq = t->nq, mr = e->cfg.max_results;
-    std::memcpy(rows, t->rows.p, (size_t)nq * mr * sizeof(aid_match_row));
-    const int64_t *starts = t->meta.p, *counts = starts + nq, *votes = counts + nq;
-    std::vector<int> again;
-    int n_light = 0;
-    for (int q = 0; q < nq; ++q) {
-        const int32_t n = t->nrows.p[q];
-        if (n < 0) {
-            again.push_back(q);
-            ++e->st_fb_reason[std::min(-n, 5) - 1];
-        } else {
-            nrows[q] = n;
-        }
-        e->st_votes += votes[q];
-        e->st_records += counts[q];
-        e->st_sig_reads += votes[q] <= kLdsMaxVotes ? 2 * votes[q] : 0;
-        n_light += votes[q] <= kLdsMaxVotes;
-    }
-    e->st_queries += nq;
-    e->st_q_lds += n_light;
-    e->n_fallback += (int64_t)again.size();
-    if (again.empty()) return AID_OK;
-    // the queries the LDS path handed back: the global path over the ticket's own copy of their records
-    HIP_TRY(hipSetDevice(e->device));
-    const int na = (int)again.size();
-    std::vector<int64_t> sc(2 * (size_t)na);
-    for (int i = 0; i < na; ++i) {
-        sc[i] = starts[again[i]];
-        sc[na + i] = counts[again[i]];
-    }
-    HIP_TRY(t->qsc.reserve((size_t)2 * nq));
-    HIP_TRY(hipMemcpyAsync(t->qsc.p, sc.data(), sc.size() * sizeof(int64_t), hipMemcpyHostToDevice, t->s));
-    std::vector<aid_match_row> sub((size_t)na * mr);
-    std::vector<int32_t> subn(na, 0);
-    const int keep_path = e->k5_path;
-    const int64_t q0 = e->st_queries, v0 = e->st_votes, r0 = e->st_records;
-    e->k5_path = 2;
-    const int rc = run_queries(e, t->recs.p, t->qsc.p, t->qsc.p + na, na, t->nrec, sub.data(), subn.data(), t->s);
-    e->k5_path = keep_path;
-    e->st_queries = q0;  // counted above already
-    e->st_votes = v0;
-    e->st_records = r0;
-    if (rc) return rc;
-    for (int i = 0; i < na; ++i) {
-        nrows[again[i]] = subn[i];
-        std::memcpy(rows + (size_t)again[i] * mr, sub.data() + (size_t)i * mr, (size_t)mr * sizeof(aid_match_row));
-    }
-    return AID_OK;
-}
-
-static int query_windows_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *starts,
-                               const int64_t *ends, int32_t n_windows, aid_match_row *rows, int32_t *nrows,
-                               void *stream) {
-    if (!e || n_windows < 0 || (n_windows > 0 && (!starts || !ends || !rows || !nrows)))
-        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
-    for (int c = 0; c < n_windows; ++c)
-        if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, std::string(fn) + ": bad window");
-    if (n_windows > 0 && !pcm) return fail(AID_ERR_INVALID, std::string(fn) + ": null pcm");
-    if (n_windows == 0) return AID_OK;
-    // one critical section, as aid_query_pcm: K1 reads every window in place (they may overlap), then K5
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = ensure_index(e)) return rc;
-    if (int rc = extract_locked(e, pcm, fmt, starts, n_windows, AID_PCM_DEVICE, stream, ends)) return rc;
-    return query_extracted_locked(e, rows, nrows);
-}
-
-int aid_query_windows(aid_engine *e, const float *pcm, const int64_t *starts, const int64_t *ends, int32_t n_windows,
-                      aid_match_row *rows, int32_t *nrows, void *stream) {
-    return query_windows_entry("aid_query_windows", e, pcm, kF32, starts, ends, n_windows, rows, nrows, stream);
-}
-
-int aid_query_windows_s16(aid_engine *e, const int16_t *pcm, const int64_t *starts, const int64_t *ends,
-                          int32_t n_windows, aid_match_row *rows, int32_t *nrows, void *stream) {
-    return query_windows_entry("aid_query_windows_s16", e, pcm, kS16, starts, ends, n_windows, rows, nrows, stream);
-}
-
 }  // extern "C"
 
 extern "C" int aid_downmix(aid_engine *e, const float *stereo, int64_t n_frames, float *mono, void *stream) {
@@ -2890,146 +1977,3 @@ extern "C" int aid_downmix(aid_engine *e, const float *stereo, int64_t n_frames,
     HIP_TRY(hipGetLastError());
     return AID_OK;
 }
-
-// ---------------------------------------------------------------- batched exact lane
-
-extern "C" int aid_exact_windows(int64_t n, int32_t sample_rate, int64_t *lo, int64_t *len, int32_t *mode) {
-    if (n < 0 || sample_rate <= 0 || !lo || !len || !mode) return fail(AID_ERR_INVALID, "aid_exact_windows: bad argument");
-    // app/search/exact.py: duration = samples / SAMPLE_RATE (:389-390); <= 5.0 s -> SUB_WINDOWS
-    // (:48-52, :103), stop = min(b, duration), piece = _extract_pcm_window(a, stop) if a < stop
-    // (:150-160), whose byte bounds are int(t * SAMPLE_RATE) * 4 clamped to the data (:374-399)
-    static const double kSub[3][2] = {{0.0, 3.5}, {0.75, 4.25}, {1.5, 5.0}};
-    const double sr = (double)sample_rate, dur = (double)n / sr;
-    if (!(dur <= 5.0)) {
-        *mode = 0;
-        lo[0] = 0;
-        len[0] = n;
-        return 1;
-    }
-    *mode = 1;
-    for (int w = 0; w < 3; ++w) {
-        const double a = kSub[w][0], stop = std::min(kSub[w][1], dur);
-        int64_t l = 0, h = 0;
-        if (a < stop) {
-            l = std::min(std::max<int64_t>((int64_t)(a * sr), 0), n);
-            h = std::max(l, std::min<int64_t>((int64_t)(stop * sr), n));
-        }
-        lo[w] = l;
-        len[w] = h - l;  // 0: the reference sends no query for this window
-    }
-    return 3;
-}
-
-static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream);
-
-static int exact_lane_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
-                            int32_t n_clips, int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out,
-                            void *stream) {
-    if (!e || !offsets || n_clips < 0 || max_out <= 0 || (n_clips > 0 && (!out || !n_out)))
-        return fail(AID_ERR_INVALID, std::string(fn) + ": bad argument");
-    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
-    if (e->cfg.max_results > 256) return fail(AID_ERR_INVALID, std::string(fn) + ": engine max_results must be <= 256");
-    if (n_clips == 0) return AID_OK;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return drain_host_copy(e, loc, stream,
-                           exact_lane_locked(e, pcm, fmt, offsets, n_clips, loc, max_out, out, n_out, stream));
-}
-
-extern "C" int aid_exact_lane(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                              int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
-    return exact_lane_entry("aid_exact_lane", e, pcm, kF32, offsets, n_clips, loc, max_out, out, n_out, stream);
-}
-
-extern "C" int aid_exact_lane_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
-                                  int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
-    return exact_lane_entry("aid_exact_lane_s16", e, pcm, kS16, offsets, n_clips, loc, max_out, out, n_out, stream);
-}
-
-static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = ensure_index(e)) return rc;
-    hipStream_t s = pick_stream(e, stream);
-    if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    // fan-out plan (host): clip_win = (first window, windows, mode). A window of odd length n is
-    // extracted as n - 1 samples: with an even hop, frames(n) = frames(n - 1) for odd n and no
-    // frame reaches the last sample, so the records are the same. K1 reads the windows in place
-    // (wstart / wend into the clips' PCM; at 44.1 kHz the 0.75 s window starts at an odd sample);
-    // the LANE_GATHER A/B copies them to even offsets of a staging buffer first (xoff)
-    std::vector<int64_t> wdesc, xoff(1, 0), wstart, wend;
-    std::vector<int32_t> clipwin(3 * (size_t)n_clips);
-    int64_t staged = 0, max_len = 0;
-    for (int c = 0; c < n_clips; ++c) {
-        int64_t lo[3], len[3];
-        int32_t mode = 0;
-        const int nw = aid_exact_windows(offsets[c + 1] - offsets[c], e->cfg.sample_rate, lo, len, &mode);
-        clipwin[3 * c] = (int32_t)(xoff.size() - 1);
-        int used = 0;
-        for (int w = 0; w < nw; ++w) {
-            if (len[w] <= 0) continue;  // the reference sends no query for an empty piece
-            const int64_t m = len[w] & ~(int64_t)1;
-            wdesc.push_back(offsets[c] - offsets[0] + lo[w]);
-            wdesc.push_back(m);
-            wdesc.push_back(staged);
-            wstart.push_back(offsets[c] - offsets[0] + lo[w]);
-            wend.push_back(offsets[c] - offsets[0] + lo[w] + m);
-            staged += m;
-            xoff.push_back(staged);
-            max_len = std::max(max_len, m);
-            ++used;
-        }
-        clipwin[3 * c + 1] = used;
-        clipwin[3 * c + 2] = mode;
-    }
-    const int n_win = (int)(xoff.size() - 1);
-    const void *src = pcm_at(pcm, fmt, offsets[0]);
-    if (loc == AID_PCM_HOST) {
-        const int64_t n_all = offsets[n_clips] - offsets[0];
-        const size_t nbytes = (size_t)n_all * pcm_size(fmt);  // x_in is raw bytes to both formats
-        HIP_TRY(e->x_in.reserve(std::max<size_t>((nbytes + sizeof(float) - 1) / sizeof(float), 1)));
-        if (n_all > 0) HIP_TRY(hipMemcpyAsync(e->x_in.p, src, nbytes, hipMemcpyHostToDevice, s));
-        src = e->x_in.p;
-    }
-    HIP_TRY(e->x_clipwin.reserve(clipwin.size()));
-    HIP_TRY(hipMemcpyAsync(e->x_clipwin.p, clipwin.data(), clipwin.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(e->x_nout.reserve((size_t)n_clips));
-    HIP_TRY(e->x_out.reserve((size_t)n_clips * max_out * 3));
-    std::vector<int32_t> nrows(std::max(n_win, 1), 0);
-    const int mr = e->cfg.max_results;
-    if (n_win > 0) {
-        if (e->lane_gather) {
-            HIP_TRY(e->x_wdesc.reserve(wdesc.size()));
-            HIP_TRY(hipMemcpyAsync(e->x_wdesc.p, wdesc.data(), wdesc.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            HIP_TRY(e->x_win.reserve((size_t)std::max<int64_t>(staged, 2)));
-            // the gather converts s16 windows on the way: the staged windows are float to either format
-            launch_window_gather(src, fmt == kS16, e->x_wdesc.p, n_win, max_len, e->x_win.p, s);
-            HIP_TRY(hipGetLastError());
-            if (int rc = extract_locked(e, e->x_win.p, kF32, xoff.data(), n_win, AID_PCM_DEVICE, s)) return rc;
-        } else {
-            if (int rc = extract_locked(e, src, fmt, wstart.data(), n_win, AID_PCM_DEVICE, s, wend.data())) return rc;
-        }
-        if (int rc = check_query_frames(e)) return rc;
-        HIP_TRY(e->q_start.reserve(n_win));
-        HIP_TRY(upload_clip_base(e, n_win, s));
-        if (int rc = run_queries(e, e->records.p, e->q_start.p, e->counts.p, n_win, (int64_t)e->records.n, nullptr,
-                                 nrows.data(), s))
-            return rc;
-        HIP_TRY(e->q_nrows.reserve((size_t)n_win));
-        HIP_TRY(hipMemcpyAsync(e->q_nrows.p, nrows.data(), n_win * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    } else {
-        HIP_TRY(e->q_nrows.reserve(1));
-        HIP_TRY(e->q_rows.reserve((size_t)mr * 5));
-        HIP_TRY(hipMemsetAsync(e->q_nrows.p, 0, sizeof(int32_t), s));
-    }
-    const double sec = (double)e->cfg.hop / (double)e->cfg.sample_rate;
-    launch_exact_consensus(e->q_rows.p, e->q_nrows.p, mr, e->x_clipwin.p, n_clips, sec, max_out, e->x_out.p, e->x_nout.p,
-                           s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(n_out, e->x_nout.p, (size_t)n_clips * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out, e->x_out.p, (size_t)n_clips * max_out * sizeof(aid_exact_row), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    e->last_stream = s;
-    return AID_OK;
-}
-

@@ -1,0 +1,327 @@
+// engine_internal.h -- what the host files of libaidfp.so share: the engine's state (struct aid_engine), its buffer
+// and profiling helpers, and the few functions engine.cpp (engine, extraction, index, comm) and query.cpp (K5, the
+// query entry points, the exact lane) call across the file boundary. Nothing here is part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/aidfp.h"
+#include "aidfp_device.h"
+#include "aidfp_launch.h"
+#include "aidfp_layout.h"
+#include "aidfp_vector.h"
+
+#pragma GCC visibility push(hidden)  // shared between the host files, not exported
+
+using namespace aid;
+
+int fail(int code, const std::string &msg);  // engine.cpp: keeps msg for aid_last_error, returns code
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return fail(_e == hipErrorOutOfMemory ? AID_ERR_NOMEM : AID_ERR_DEVICE,                \
+                        std::string(#expr) + ": " + hipGetErrorString(_e));                        \
+    } while (0)
+
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;  // capacity in elements
+    hipError_t reserve(size_t want) {
+        if (want <= n) return hipSuccess;
+        if (p) {  // growing: in-flight work of earlier calls may still use the old buffer
+            (void)hipDeviceSynchronize();
+            (void)hipFree(p);
+        }
+        p = nullptr;
+        n = 0;
+        size_t cap = std::max(want, (size_t)1);
+        hipError_t e = hipMalloc(&p, cap * sizeof(T));
+        if (e == hipSuccess) n = cap;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+// page-locked host buffer (hipHostMalloc): device-to-host copies into it are asynchronous, so a call can queue its
+// result copies behind its kernels and wait once
+template <typename T>
+struct HostBuf {
+    T *p = nullptr;
+    size_t n = 0;  // capacity in elements
+    hipError_t reserve(size_t want) {  // callers have synchronised any copy still targeting the old buffer
+        if (want <= n) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        const size_t cap = std::max(want, (size_t)64);
+        hipError_t e = hipHostMalloc((void **)&p, cap * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) n = cap;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+// K5's page-locked result block: a call queues the copies into it behind its kernels and waits once. The engine
+// owns one (the synchronous calls), every aid_query_ticket its own
+struct K5Host {
+    HostBuf<int64_t> meta;   // [0, nq) record starts, [nq, 2nq) record counts, [2nq, 3nq) exact votes
+    HostBuf<int32_t> rows;   // the LDS pass's rows, [nq][max_results][5]
+    HostBuf<int32_t> nrows;  // the LDS pass's row counts; -r: handed back for reason r (index.hip)
+    void release() {
+        meta.release();
+        rows.release();
+        nrows.release();
+    }
+};
+
+struct ProfEvent {
+    int kernel;
+    hipEvent_t a, b;
+};
+
+struct aid_engine {
+    aid_config cfg{};
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    Tables *d_tab = nullptr;
+    int16_t *d_sin = nullptr;
+
+    DevBuf<float> pcm_stage;
+    DevBuf<float> power;
+    DevBuf<uint64_t> mask;
+    DevBuf<uint64_t> hotw;  // K1 -> K2: per power row, bit hot_bit(c) = 16-bin chunk c has a value > thr
+    // FPSPEC 5.1 (cfg.peak_rel > 0): per clip of the call, the bit pattern of max Q over its plane. Zeroed on the
+    // call's stream before the first K1, raised by K1's atomics, read by K2 and aid_result_thresholds
+    DevBuf<uint32_t> clip_qmax;
+    DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3
+    // pinned, host-mapped, two words: K3 stores (cold waves | waves << 32) and (twice-walked strips | strips << 32) of
+    // the last K2 here; waves / strips is the width that K2 ran at
+    uint64_t *h_cold = nullptr;
+    uint64_t *h_cold_dev = nullptr;  // its device address
+    int k2_width_force = 0;          // aid_engine_force K2_WIDTH: 2 or 4 quarter waves per K2 workgroup; 0 = adaptive
+    int k2_width = 4;                // the adaptive choice (extract_locked); also the width of the last call
+    int k2_hold = 0;                 // calls left at width 4 after a fall-back from width 2 (hysteresis)
+    double k2_slots_x = 0.0;         // aid_engine_force K2_STRIPS: fixed strips per slot; 0 = adaptive (extract_locked)
+    DevBuf<ClipDesc> desc;
+    DevBuf<int64_t> chunk_counts;
+    DevBuf<uint64_t> records;
+    DevBuf<int64_t> counts;
+    DevBuf<uint32_t> synth_tracks;
+    DevBuf<int64_t> synth_starts;
+    uint8_t *h_synth = nullptr;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
+    size_t h_synth_cap = 0;
+    hipEvent_t synth_ev = nullptr;
+    bool synth_ev_live = false;
+
+    // index (FPSPEC 7): all postings (SoA source of truth) + the CSR built from them
+    DevBuf<uint32_t> p_hash, p_track, p_t;
+    int64_t n_post = 0;  // exact unless post_pend: then the last aid_index_add_extracted's count is in flight
+    // aid_index_add_extracted appends without waiting for its clips' counts: K_append scans them on the device and
+    // the new total comes back to pinned h_npost behind add_ev; settle_postings() makes n_post exact again
+    DevBuf<int64_t> d_npost;
+    int64_t *h_npost = nullptr;
+    hipEvent_t add_ev = nullptr;  // after the last append's staging copies (and, if post_pend, its count copy)
+    bool add_live = false, post_pend = false;
+    std::vector<uint8_t> h_tomb;  // per track id: 1 = removed
+    DevBuf<uint8_t> tomb;
+    uint32_t n_tracks = 0;        // max track id + 1
+    DevBuf<uint32_t> idx_cnt, idx_off, scan_tmp;
+    DevBuf<uint64_t> idx_post;
+    DevBuf<uint16_t> idx_sig;  // K5's 2-B vote signature per CSR posting (aidfp_layout.h posting_sig)
+    DevBuf<uint32_t> srt_k0, srt_k1;  // K4 sort build: key double buffer
+    DevBuf<uint64_t> srt_v;           // K4 sort build: the value buffer idx_post pairs with
+    DevBuf<uint8_t> srt_tmp;          // K4 rocPRIM build (A/B): its temporary storage
+    DevBuf<uint32_t> srt_scratch;     // K4 radix build: per-tile digit counts, their scan, scan temporary
+    int k4_mode = 2;                  // internal K4 build: 2 radix sort (the default; K4_BUILD force 0, 1 or 4),
+                                      // 1 rocPRIM sort (force 3, variant build only), 0 atomic counting sort (force 2)
+    int k4_rank = 0;                  // radix sort's in-wave rank: 0 one LDS atomic per posting where the device
+                                      // serves same-address lanes in order (else ballots), 1 ballots (K4_BUILD 4)
+    bool index_built = false, index_dirty = true;
+    int64_t n_indexed = 0;
+    DevBuf<unsigned long long> nz;
+    DevBuf<unsigned long long> chk;  // aid_index_checksum result
+    // query workspaces
+    DevBuf<uint64_t> q_recs;
+    DevBuf<int64_t> q_start, q_count;
+    DevBuf<uint32_t> q_hist;
+    DevBuf<int32_t> q_rows, q_nrows;
+    DevBuf<uint32_t> q_hot;  // K5h hot-bucket bitmaps, [batch][2^bits / 32]
+    DevBuf<uint32_t> q_dset;  // K5b retries: HBM distinct (slot, t_q) sets, [batch][2^dbits]
+    DevBuf<uint64_t> q_ranges;  // K5: per query record its CSR range (k_query_votes -> k_match_lds)
+    K5Host k5h;                 // run_queries: the synchronous calls' result block
+    HostBuf<int64_t> hq_start;  // the queries' record starts (clip_base) staged page-locked for their upload
+    std::vector<aid_query_ticket *> ticket_pool;  // collected tickets, reused: their buffers and event stay allocated
+    DevBuf<int64_t> q_votes;  // exact votes per query (LDS-histogram eligibility)
+    DevBuf<int64_t> x_src, x_dst;
+    // batched exact lane (aid_exact_lane): PCM staging, window descriptors, consensus output
+    DevBuf<float> x_in, x_win;
+    DevBuf<int64_t> x_wdesc;
+    DevBuf<int32_t> x_order, x_clipwin, x_nout;
+    DevBuf<double> x_out;  // aid_exact_row, 3 x 8 bytes each
+    DevBuf<int64_t> g_meta;            // all-gather: (count, n_tracks) per rank
+    std::map<std::pair<int32_t, int32_t>, float *> rs_taps;  // (up, down) -> device [up][J] taps
+    // Chromaprint dedup catalog (insertion order) + scan scratch
+    DevBuf<uint32_t> dd_words;
+    DevBuf<int64_t> dd_off;
+    DevBuf<double> dd_dur;
+    int64_t dd_n = 0, dd_nw = 0;
+    DevBuf<uint32_t> dq_words, dq_words2;
+    DevBuf<int64_t> dq_off, dq_off2, dq_idx, dq_pidx;
+    DevBuf<double> dq_lo, dq_hi, dq_sim, dq_psim;
+    VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
+    DevBuf<uint32_t> g_send, g_recv;   // all-gather: [3][max] SoA planes per rank
+    DevBuf<uint32_t> x_tracks;
+    size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
+
+    int64_t *h_stage = nullptr;  // pinned staging of aid_index_add_extracted
+    size_t h_stage_cap = 0;
+    ClipDesc *h_desc = nullptr;  // pinned
+    size_t h_desc_cap = 0;
+    // extraction call hazards, tracked with events instead of a stream sync per call:
+    // h_desc is the source of an async H2D copy; pcm_stage is read by K1
+    hipEvent_t desc_ev = nullptr, stage_ev = nullptr;
+    bool desc_ev_live = false, stage_ev_live = false;
+    hipStream_t stage_stream = nullptr;  // the stream whose K1 read pcm_stage last
+    std::vector<int64_t> desc_key;  // offsets (+ pcm location) the device descriptors were built for
+    ClipDesc *desc_dev_for_key = nullptr;
+    std::vector<int64_t> clip_base;  // host copy of desc[c].hash_base
+    std::vector<int64_t> clip_frames;
+    int n_clips = 0;
+    int64_t total_frames = 0, total_strips = 0, total_chunks = 0, total_records = 0;
+    int64_t k2_slots[2] = {1, 1};  // resident K2 workgroups on the device (CUs x blocks per CU) at width 2, 4
+    int64_t k1_slots = 1;  // resident K1 waves (CUs x kStftWaves: one K1 workgroup per CU)
+    // aid_engine_force K5_PATH (tests): 0 the LDS pass, then the global path for the queries it hands back; 1 as 0
+    // (kept for callers that pin the LDS path); 2 global path only. The submit/collect pair ignores it
+    int k5_path = 0;
+    int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
+    int lane_gather = 0;           // aid_engine_force LANE_GATHER: stage the exact lane's sub-windows (A/B)
+    int64_t plane_rows = 0;        // aid_engine_force PLANE_ROWS: power rows per K1 -> K2 clip group (0 = kPlaneRows)
+    int inject_exchange_fail = 0;  // aid_engine_force EXCHANGE_FAIL: the next exchange's prepare step fails (tests)
+    // aid_match_stats: queries, exact votes, and the postings K5 read (a vote = one 8-B posting per pass)
+    int64_t st_queries = 0, st_votes = 0, st_post_reads = 0, st_q_global = 0, st_q_lds = 0, st_records = 0;
+    int64_t st_sig_reads = 0;  // 2-B posting signatures the LDS path read (two per vote: counting and insert passes)
+    int64_t st_fb_reason[5] = {0, 0, 0, 0, 0};  // LDS-path fallbacks (speculative pass) by reason (index.hip)
+    int64_t tomb_since_build = 0;  // removals after the last CSR build (queries must check tomb[])
+    size_t k5_batch = 2048;        // global-path queries per launch
+    hipStream_t last_stream = nullptr;
+    bool have_result = false;
+
+    bool profiling = false;
+    uint32_t prof_mask = 0xFFFFFFFFu;  // bit k: kernel id k gets events (aid_profile_select)
+    std::vector<ProfEvent> pending;
+    std::vector<hipEvent_t> pool;
+    double prof_ms[AID_K_COUNT] = {};
+    int64_t prof_n[AID_K_COUNT] = {};
+    std::mutex mu;
+};
+
+static inline hipEvent_t take_event(aid_engine *e) {
+    if (!e->pool.empty()) {
+        hipEvent_t ev = e->pool.back();
+        e->pool.pop_back();
+        return ev;
+    }
+    hipEvent_t ev = nullptr;
+    if (hipEventCreate(&ev) != hipSuccess) return nullptr;
+    return ev;
+}
+
+// attached = the scope wraps exactly one timed_launch: its events are stamped by the dispatch itself
+// (aidfp_device.h LaunchTiming); otherwise two hipEventRecord markers bracket the scope.
+struct ProfScope {
+    aid_engine *e;
+    int k;
+    hipStream_t s;
+    bool attached;
+    hipEvent_t a = nullptr, b = nullptr;
+    ProfScope(aid_engine *e_, int k_, hipStream_t s_, bool attached_ = false) : e(e_), k(k_), s(s_), attached(attached_) {
+        if (!e->profiling || !((e->prof_mask >> k) & 1u) || !(a = take_event(e))) return;
+        if (!attached) {
+            (void)hipEventRecord(a, s);
+            return;
+        }
+        if (!(b = take_event(e))) {
+            e->pool.push_back(a);
+            a = nullptr;
+            return;
+        }
+        launch_timing().start = a;
+        launch_timing().stop = b;
+    }
+    ~ProfScope() {
+        if (!a) return;
+        if (attached) {
+            LaunchTiming &t = launch_timing();
+            if (t.start) {  // nothing was launched: the events were never stamped
+                t.start = t.stop = nullptr;
+                e->pool.push_back(a);
+                e->pool.push_back(b);
+                return;
+            }
+        } else {
+            if (!(b = take_event(e))) return;
+            (void)hipEventRecord(b, s);
+        }
+        e->pending.push_back({k, a, b});
+    }
+};
+
+static inline hipStream_t pick_stream(aid_engine *e, void *stream) {
+    return stream ? (hipStream_t)stream : e->own_stream;
+}
+
+// A host-PCM call copies the caller's samples with ONE hipMemcpyAsync on the call's stream; from page-locked
+// memory that copy is a real DMA that can still be running when the call returns. On success the caller syncs
+// before reusing its buffer (include/aidfp.h); on an error return the engine drains the stream itself, so a
+// caller that reuses or frees its buffer after a failed call cannot race the copy. Returns rc.
+static inline int drain_host_copy(aid_engine *e, int32_t loc, void *stream, int rc) {
+    if (rc != AID_OK && loc == AID_PCM_HOST && e) (void)hipStreamSynchronize(pick_stream(e, stream));
+    return rc;
+}
+
+// PCM sample format of an entry point (FPSPEC 8). The float functions and their _s16 twins funnel into one
+// implementation each, which takes the samples as const void * plus the format; offsets count samples either way
+enum PcmFmt : int { kF32 = 0, kS16 = 1 };
+static inline size_t pcm_size(PcmFmt f) { return f == kS16 ? sizeof(int16_t) : sizeof(float); }
+static inline const void *pcm_at(const void *p, PcmFmt f, int64_t i) {
+    return static_cast<const char *>(p) + i * (int64_t)pcm_size(f);
+}
+
+// the argument checks every clip-batch entry point shares (fn = its name, for the message)
+static inline int check_clips(const char *fn, aid_engine *e, const void *pcm, const int64_t *offsets, int32_t n_clips,
+                              int32_t loc) {
+    const std::string f(fn);
+    if (!e || !offsets || n_clips < 0) return fail(AID_ERR_INVALID, f + ": bad argument");
+    if (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, f + ": bad pcm_location");
+    for (int c = 0; c < n_clips; ++c)
+        if (offsets[c + 1] < offsets[c] || offsets[c] < 0)
+            return fail(AID_ERR_INVALID, f + ": offsets must be non-decreasing and >= 0");
+    if (n_clips > 0 && !pcm && offsets[n_clips] > offsets[0]) return fail(AID_ERR_INVALID, f + ": null pcm");
+    return AID_OK;
+}
+
+// engine lock held, all three; defined among their file's extern "C" functions, hence the linkage
+extern "C" {
+int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                   void *stream, const int64_t *ends = nullptr);  // engine.cpp
+int ensure_index(aid_engine *e);       // engine.cpp: (re)builds the CSR if postings changed since the last build
+void free_ticket_pool(aid_engine *e);  // query.cpp
+}  // extern "C"
+
+#pragma GCC visibility pop

@@ -17,6 +17,7 @@
 // the A/B behind aid_engine_force(LANE_GATHER). K8b `exact_consensus` runs one wave per clip over
 // the K5 rows of its windows (<= 3 x max_results rows, staged in LDS).
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

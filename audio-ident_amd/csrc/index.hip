@@ -24,6 +24,7 @@
 //        (count desc, track asc) and writes at most max_rows; it re-zeroes its
 //        histogram row for the next batch.
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 
@@ -111,8 +112,6 @@ __global__ __launch_bounds__(1024) void k_scan_add(uint32_t *__restrict__ out, c
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
     if (i < n) out[i] += boff[blockIdx.x];
 }
-
-void launch_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t s);
 
 // K5's 2-B vote signatures of the CSR's postings (aidfp_layout.h posting_sig), for the builds that do not write
 // them in their last pass (the atomic build and the rocPRIM A/B; the radix build fuses it)

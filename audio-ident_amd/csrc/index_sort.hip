@@ -41,6 +41,7 @@
 #endif
 
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 
@@ -578,8 +579,6 @@ __global__ void k_sort_keys(const uint32_t *__restrict__ ph, const uint32_t *__r
     }
 }
 #endif
-
-void launch_make_sig(const uint64_t *post, int64_t n, uint16_t *sig, hipStream_t s);  // index.hip
 
 int64_t radix_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
 

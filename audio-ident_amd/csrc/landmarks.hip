@@ -18,6 +18,7 @@
 // stores records {hash, t1} in canonical order. Chunk 0 of a clip also writes the
 // clip's record count.
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

@@ -36,6 +36,7 @@
 // writes their zero mask words. The 16 bins past the group's edge (chunk 32 for the lower group, 31 for the upper)
 // are staged into the row pads only when that chunk is hot somewhere in the strip.
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

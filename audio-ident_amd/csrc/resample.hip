@@ -9,6 +9,7 @@
 // [up][J] tap table, itself staged in LDS when it fits 48 KB (else read from L1/L2). HBM traffic is the algorithmic
 // minimum: input once (+ the J-sample window overlap per block) and output once.
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

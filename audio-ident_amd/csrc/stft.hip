@@ -25,6 +25,7 @@
 // The variants measured against this layout live in the git history
 // (commit c236449, the AID_K1_* switches).
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 #include <type_traits>
 

@@ -4,6 +4,7 @@
 // m[i] = (L[i] + R[i]) * 0.5f (two correctly rounded binary32 ops; the *0.5 is exact).
 // HBM-bound: 8 B in + 4 B out per sample frame, float4 loads / float2 stores.
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

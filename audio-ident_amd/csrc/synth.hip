@@ -3,6 +3,7 @@
 // bit). Used to put the benchmark and ingest catalogs straight into HBM
 // ("generated on device").
 #include "aidfp_device.h"
+#include "aidfp_launch.h"
 
 namespace aid {
 

@@ -99,7 +99,7 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
 
 /* Test hook: force one of the engine's own code paths, which it otherwise chooses itself per call
    (the parity tests run every path against the oracle). Never needed in production. */
-#define AID_FORCE_K5_PATH 1        /* 0 auto, 1 LDS vote table first, 2 global histogram only */
+#define AID_FORCE_K5_PATH 1        /* 0 auto, 1: as 0; kept for callers that pin the LDS path, 2 global histogram only */
 #define AID_FORCE_K5_PARTS 2       /* 0 by vote count, else 1, 2 or 4 key partitions per query (K5a) */
 #define AID_FORCE_K5_BATCH 3       /* 0 default (2048), else global-path queries per launch */
 #define AID_FORCE_K2_STRIPS_X100 4 /* 0 adaptive, else 100 x K2 strips per resident workgroup slot */

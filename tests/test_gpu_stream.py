@@ -241,36 +241,117 @@ def test_stream_bank_pipelined_equals_sync():
                     assert np.array_equal(x.rows, y.rows)
 
 
-def test_query_windows_submit_collect_with_fallbacks():
+FB_SSR = 16000
+HANDBACKS = ("fallback_table", "fallback_distinct", "fallback_tracks", "fallback_rows")
+
+
+@pytest.fixture(scope="module")
+def fallback_catalog():
+    """A catalog whose queries the fast match path hands back (min_match 1: every bucket is hot, so its tables fill):
+    (engine, 4 x 20 s of device PCM, window starts, window ends), five windows of 5 to 9 s. Ingested once."""
+    from aidfp.catalog import ingest_synthetic
+
+    with Engine(FB_SSR, min_match=1) as eng:
+        ingest_synthetic(eng, np.arange(1200, dtype=np.uint32), 30.0, batch=256, source_sr=44100, local=True)
+        eng.index_finalize()
+        n = 20 * FB_SSR
+        pcm = torch.empty(4 * n, dtype=torch.float32, device="cuda")
+        eng.synth(pcm.data_ptr(), np.array([3, 77, 150, 299], np.uint32), np.zeros(4, np.int64), n,
+                  noise_a=synth.noise_halfwidth(20.0), salt=5, sample_rate=FB_SSR)
+        torch.cuda.synchronize()
+        st = np.array([0, 7 * FB_SSR, n + 3 * FB_SSR, 2 * n + 11, 3 * n + 5 * FB_SSR], np.int64)
+        en = st + np.array([5, 5, 5, 9, 5], np.int64) * FB_SSR
+        yield eng, pcm, st, en
+
+
+def _handbacks(ms):
+    return sum(ms[k] for k in HANDBACKS)
+
+
+def test_query_windows_submit_collect_with_fallbacks(fallback_catalog):
     """Two tickets in flight, collected out of order, and queries the fast match path hands back (min_match 1: more
     candidate tracks than its row staging holds): rows equal aid_query_windows' (which takes the global path for them
     too) and the oracle's."""
     import oracle as O
-    from aidfp.catalog import ingest_synthetic
 
-    SSR = 16000
-    with Engine(SSR, min_match=1) as eng:
-        ingest_synthetic(eng, np.arange(1200, dtype=np.uint32), 30.0, batch=256, source_sr=44100, local=True)
-        eng.index_finalize()
-        n = 20 * SSR
-        pcm = torch.empty(4 * n, dtype=torch.float32, device="cuda")
-        eng.synth(pcm.data_ptr(), np.array([3, 77, 150, 299], np.uint32), np.zeros(4, np.int64), n,
-                  noise_a=synth.noise_halfwidth(20.0), salt=5, sample_rate=SSR)
-        st = np.array([0, 7 * SSR, n + 3 * SSR, 2 * n + 11, 3 * n + 5 * SSR], np.int64)
-        en = st + np.array([5, 5, 5, 9, 5], np.int64) * SSR
+    eng, pcm, st, en = fallback_catalog
+    eng.match_stats(reset=True)
+    want = eng.query_windows(pcm.data_ptr(), st, en)
+    a = eng.query_windows_submit(pcm.data_ptr(), st[:3], en[:3])
+    b = eng.query_windows_submit(pcm.data_ptr(), st[3:], en[3:])
+    gb, ga = b.collect(), a.collect()
+    ms = eng.match_stats()
+    # the case under test: the LDS path handed some queries back (every bucket is hot at min_match 1, so its
+    # tables fill) and collect answered them on the global path
+    assert sum(ms[k] for k in ("fallback_table", "fallback_distinct", "fallback_tracks", "fallback_rows")) > 0, ms
+    for w, g in zip(want, ga + gb):
+        assert np.array_equal(w, g)
+    post = eng.index_export()
+    host = pcm.cpu().numpy()
+    for k in range(len(st)):
+        rec = O.fingerprint(host[st[k]:en[k]], 256)
+        assert np.array_equal(want[k], O.query(post, rec, min_match=1, max_rows=eng.max_results))
+
+
+def test_match_stats_agree_sync_and_tickets(fallback_catalog):
+    """aid_match_stats counts a batch the same whether aid_query_windows answers it or two tickets do: every query,
+    vote, record, signature read, path split and hand-back reason once. (Every query here is far below 2^18 votes,
+    so both paths run the global pass with one key partition and posting_reads agree too.)"""
+    eng, pcm, st, en = fallback_catalog
+    keys = ("queries", "votes", "records", "sig_reads", "queries_lds", "queries_global", "posting_reads",
+            "fallback_heavy") + HANDBACKS
+    eng.match_stats(reset=True)
+    eng.query_windows(pcm.data_ptr(), st, en)
+    sync = eng.match_stats(reset=True)
+    a = eng.query_windows_submit(pcm.data_ptr(), st[:3], en[:3])
+    b = eng.query_windows_submit(pcm.data_ptr(), st[3:], en[3:])
+    a.collect()
+    b.collect()
+    tick = eng.match_stats(reset=True)
+    print("sync", sync, "tickets", tick)
+    assert _handbacks(sync) > 0, sync
+    assert sync["queries"] == len(st)
+    assert {k: sync[k] for k in keys} == {k: tick[k] for k in keys}
+
+
+def test_tickets_on_two_streams_with_fallbacks(fallback_catalog):
+    """Ticket A on one stream, ticket B on a second, A collected first: A's hand-backs run on the global path (over
+    engine-wide scratch) after B's work was queued on the other stream; rows equal aid_query_windows'."""
+    eng, pcm, st, en = fallback_catalog
+    want = eng.query_windows(pcm.data_ptr(), st, en)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    eng.match_stats(reset=True)
+    a = eng.query_windows_submit(pcm.data_ptr(), st[:3], en[:3], stream=s1.cuda_stream)
+    b = eng.query_windows_submit(pcm.data_ptr(), st[3:], en[3:], stream=s2.cuda_stream)
+    ga = a.collect()
+    gb = b.collect()
+    ms = eng.match_stats()
+    assert _handbacks(ms) > 0, ms
+    got = ga + gb
+    assert len(got) == len(want)
+    for w, g in zip(want, got):
+        assert np.array_equal(w, g)
+
+
+def test_exact_lane_device_rows_with_handbacks(fallback_catalog):
+    """The exact lane keeps K5's rows on the device; when the fast match path hands back only some of its windows,
+    their rows from the global path are scattered into the batch's slots: results equal the global-only run's."""
+    eng, pcm, st, en = fallback_catalog
+    n = 20 * FB_SSR
+    host = pcm.cpu().numpy()
+    clips = [host[i * n + FB_SSR: i * n + 6 * FB_SSR] for i in range(4)]  # 5 s: three sub-windows each
+    try:
+        eng.force("k5_path", 0)
         eng.match_stats(reset=True)
-        want = eng.query_windows(pcm.data_ptr(), st, en)
-        a = eng.query_windows_submit(pcm.data_ptr(), st[:3], en[:3])
-        b = eng.query_windows_submit(pcm.data_ptr(), st[3:], en[3:])
-        gb, ga = b.collect(), a.collect()
-        ms = eng.match_stats()
-        # the case under test: the LDS path handed some queries back (every bucket is hot at min_match 1, so its
-        # tables fill) and collect answered them on the global path
-        assert sum(ms[k] for k in ("fallback_table", "fallback_distinct", "fallback_tracks", "fallback_rows")) > 0, ms
-        for w, g in zip(want, ga + gb):
-            assert np.array_equal(w, g)
-        post = eng.index_export()
-        host = pcm.cpu().numpy()
-        for k in range(len(st)):
-            rec = O.fingerprint(host[st[k]:en[k]], 256)
-            assert np.array_equal(want[k], O.query(post, rec, min_match=1, max_rows=eng.max_results))
+        mixed = eng.exact_lane(clips)
+        ms = eng.match_stats(reset=True)
+        eng.force("k5_path", 2)
+        glob = eng.exact_lane(clips)
+    finally:
+        eng.force("k5_path", 0)
+    print("exact lane, k5_path 0:", ms)
+    assert _handbacks(ms) > 0, ms
+    assert 0 < ms["queries_global"] < ms["queries"], ms  # a proper subset went through the scatter
+    assert len(mixed) == len(glob) == 4 and sum(len(r) for r in glob) > 0
+    for m, g in zip(mixed, glob):
+        assert np.array_equal(m, g)
