@@ -182,6 +182,7 @@ SIGNATURES = [
     ("aid_profile_enable", ctypes.c_int, [P, I32]),
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),
+    ("aid_live_allocations", ctypes.c_int, [P, P, P]),
 ]
 # the _s16 twins (integer PCM, FPSPEC 8): the sibling's signature, int16 samples behind the PCM pointer
 SIGNATURES += [(name + "_s16", res, args) for name, res, args in SIGNATURES

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/aidfp.h"
+#include "aidfp_buffers.h"
 
 namespace aid {
 
@@ -28,22 +29,14 @@ inline size_t vec_layout_index(int64_t row, int k, int dim) {
     return (size_t)(row >> 5) * 32 * dim + (size_t)(((k >> 3) * 2 + (k & 1)) * 128 + (int)(row & 31) * 4 + ((k & 7) >> 1));
 }
 
-template <typename T>
-struct VecBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t reserve(size_t want);  // contents are lost on growth
-    void release();
-};
-
 struct VecCatalog {
     int dim = 0;  // 0 until aid_vec_reset
     int64_t n = 0, n_live = 0;
     int64_t cap_rows = 0;  // multiple of 32; rows [n, cap_rows) of d_vecs are +0
-    float *d_vecs = nullptr;
-    VecBuf<uint32_t> d_track;
-    VecBuf<double> d_off;
-    VecBuf<uint8_t> d_dead;
+    DevBuf<float> d_vecs;
+    DevBuf<uint32_t, 64> d_track;
+    DevBuf<double, 64> d_off;
+    DevBuf<uint8_t, 64> d_dead;
     std::vector<uint32_t> h_track;  // host mirror of the payload columns (hits are filled from it)
     std::vector<int32_t> h_chunk;
     std::vector<double> h_off;
@@ -51,18 +44,17 @@ struct VecCatalog {
     int force_path = 0;   // AID_FORCE_VEC_PATH
     int force_chunk = 0;  // AID_FORCE_VEC_CHUNK
     // scratch
-    VecBuf<float> d_raw, d_q, d_scores;
-    VecBuf<unsigned long long> d_keys0, d_keys1, d_cand;
-    VecBuf<uint32_t> d_smax, d_thr;
-    VecBuf<int32_t> d_ccnt;
-    VecBuf<uint32_t> d_hentry, d_htrack, d_excl;
-    VecBuf<float> d_hscore;
-    VecBuf<double> d_hoff;
-    VecBuf<int32_t> d_nhits, d_cnt, d_nout;
-    VecBuf<int64_t> d_start;
-    VecBuf<aid_vibe_row> d_rows;
+    DevBuf<float, 64> d_raw, d_q, d_scores;
+    DevBuf<unsigned long long, 64> d_keys0, d_keys1, d_cand;
+    DevBuf<uint32_t, 64> d_smax, d_thr;
+    DevBuf<int32_t, 64> d_ccnt;
+    DevBuf<uint32_t, 64> d_hentry, d_htrack, d_excl;
+    DevBuf<float, 64> d_hscore;
+    DevBuf<double, 64> d_hoff;
+    DevBuf<int32_t, 64> d_nhits, d_cnt, d_nout;
+    DevBuf<int64_t, 64> d_start;
+    DevBuf<aid_vibe_row, 64> d_rows;
     std::string err;
-    void release_all();
 };
 
 int vec_reset(VecCatalog &c, int dim);

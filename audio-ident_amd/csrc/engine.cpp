@@ -104,50 +104,35 @@ int aid_engine_create(const aid_config *cfg, aid_engine **out) {
         return fail(AID_ERR_DEVICE, std::string("libaidfp is built for gfx950, device is ") + prop.gcnArchName);
     c.device = dev;
 
-    aid_engine *e = new aid_engine();
+    std::unique_ptr<aid_engine> e(new aid_engine());  // every early return below frees what was built so far
     e->cfg = c;
     e->device = dev;
     for (int w = 0; w < 2; ++w) e->k2_slots[w] = (int64_t)prop.multiProcessorCount * peak_pick_blocks_per_cu(2 + 2 * w);
     e->k1_slots = (int64_t)prop.multiProcessorCount * kStftWaves;
     // blocking stream: ordered against the legacy default stream (torch's default), so device
     // buffers the caller filled there without a stream handle are complete before NULL-stream calls
-    hipError_t he = hipStreamCreateWithFlags(&e->own_stream, hipStreamDefault);
-    if (he != hipSuccess) {
-        delete e;
-        return fail(AID_ERR_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(he));
-    }
-    Tables *h = new Tables();
+    hipError_t he = hipStreamCreateWithFlags(&e->own_stream.s, hipStreamDefault);
+    if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(he));
+    std::unique_ptr<Tables> h(new Tables());
     build_tables(*h);
     // K1 derives the real split's mirror twiddle T2K[1024-k] as (-re, im) of T2K[k]
     for (int k = 1; k < 512; ++k)
-        if (!(h->t2k[1024 - k].x == -h->t2k[k].x && h->t2k[1024 - k].y == h->t2k[k].y)) {
-            delete h;
-            (void)hipStreamDestroy(e->own_stream);
-            delete e;
+        if (!(h->t2k[1024 - k].x == -h->t2k[k].x && h->t2k[1024 - k].y == h->t2k[k].y))
             return fail(AID_ERR_DEVICE, "twiddle table lacks the mirror symmetry K1 relies on");
-        }
     // K1's DFT16 (aidfp_device.h) shares one product in the cmuls by T16[2], T16[4], T16[6]
     {
         const float2 w2 = h->t16[2], w4 = h->t16[4], w6 = h->t16[6];
-        if (!(w2.y == -w2.x && w6.x == w6.y && w6.x == -w2.x && w4.y == -1.0f)) {
-            delete h;
-            (void)hipStreamDestroy(e->own_stream);
-            delete e;
+        if (!(w2.y == -w2.x && w6.x == w6.y && w6.x == -w2.x && w4.y == -1.0f))
             return fail(AID_ERR_DEVICE, "DFT16 twiddle table lacks the symmetry K1 relies on");
-        }
     }
     std::vector<int16_t> sin_tab(4096);
     for (int k = 0; k < 4096; ++k) sin_tab[k] = (int16_t)nearbyint(32767.0 * sin(2.0 * M_PI * (double)k / 4096.0));
-    he = hipMalloc(&e->d_tab, sizeof(Tables));
-    if (he == hipSuccess) he = hipMemcpy(e->d_tab, h, sizeof(Tables), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc(&e->d_sin, 4096 * sizeof(int16_t));
-    if (he == hipSuccess) he = hipMemcpy(e->d_sin, sin_tab.data(), 4096 * sizeof(int16_t), hipMemcpyHostToDevice);
-    delete h;
-    if (he != hipSuccess) {
-        aid_engine_destroy(e);
-        return fail(AID_ERR_DEVICE, std::string("table upload: ") + hipGetErrorString(he));
-    }
-    *out = e;
+    he = e->d_tab.reserve(1);
+    if (he == hipSuccess) he = hipMemcpy(e->d_tab.p, h.get(), sizeof(Tables), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = e->d_sin.reserve(4096);
+    if (he == hipSuccess) he = hipMemcpy(e->d_sin.p, sin_tab.data(), 4096 * sizeof(int16_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("table upload: ") + hipGetErrorString(he));
+    *out = e.release();
     return AID_OK;
 }
 
@@ -159,93 +144,16 @@ void aid_engine_destroy(aid_engine *e) {
     (void)hipSetDevice(e->device);
     if (e->own_stream) (void)hipStreamSynchronize(e->own_stream);
     (void)hipDeviceSynchronize();
-    for (auto &p : e->pending) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (auto ev : e->pool) (void)hipEventDestroy(ev);
-    e->pcm_stage.release();
-    e->power.release();
-    e->k2_cold.release();
-    e->clip_qmax.release();
-    if (e->h_cold) (void)hipHostFree(e->h_cold);
-    e->mask.release();
-    e->desc.release();
-    e->chunk_counts.release();
-    e->records.release();
-    e->counts.release();
-    e->synth_tracks.release();
-    e->synth_starts.release();
-    e->p_hash.release();
-    e->p_track.release();
-    e->p_t.release();
-    e->tomb.release();
-    e->idx_cnt.release();
-    e->idx_off.release();
-    e->scan_tmp.release();
-    e->idx_post.release();
-    e->idx_sig.release();
-    e->srt_k0.release();
-    e->srt_k1.release();
-    e->srt_v.release();
-    e->srt_tmp.release();
-    e->srt_scratch.release();
-    e->nz.release();
-    e->q_recs.release();
-    e->q_start.release();
-    e->q_count.release();
-    e->q_hist.release();
-    e->q_hot.release();
-    e->q_dset.release();
-    e->q_ranges.release();
-    e->k5h.release();
-    e->hq_start.release();
-    free_ticket_pool(e);
-    e->q_rows.release();
-    e->q_nrows.release();
-    e->x_src.release();
-    e->x_dst.release();
-    e->x_in.release();
-    e->x_win.release();
-    e->x_wdesc.release();
-    e->x_order.release();
-    e->x_clipwin.release();
-    e->x_nout.release();
-    e->x_out.release();
-    e->g_meta.release();
-    for (auto &kv : e->rs_taps) (void)hipFree(kv.second);
-    e->dd_words.release();
-    e->dd_off.release();
-    e->dd_dur.release();
-    e->dq_words.release();
-    e->dq_words2.release();
-    e->dq_off.release();
-    e->dq_off2.release();
-    e->dq_idx.release();
-    e->dq_pidx.release();
-    e->dq_lo.release();
-    e->dq_hi.release();
-    e->dq_sim.release();
-    e->dq_psim.release();
-    e->vec.release_all();
-    e->g_send.release();
-    e->g_recv.release();
-    e->x_tracks.release();
-    e->chk.release();
-    if (e->h_desc) (void)hipHostFree(e->h_desc);
-    if (e->h_stage) (void)hipHostFree(e->h_stage);
-    if (e->h_synth) (void)hipHostFree(e->h_synth);
-    if (e->h_npost) (void)hipHostFree(e->h_npost);
-    e->d_npost.release();
-    if (e->synth_ev) (void)hipEventDestroy(e->synth_ev);
-    if (e->add_ev) (void)hipEventDestroy(e->add_ev);
-    if (e->desc_ev) (void)hipEventDestroy(e->desc_ev);
-    if (e->stage_ev) (void)hipEventDestroy(e->stage_ev);
-    if (e->d_tab) (void)hipFree(e->d_tab);
-    if (e->d_sin) (void)hipFree(e->d_sin);
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+    e->ticket_pool.clear();
     destroy_lk.unlock();
     delete e;
+}
+
+int aid_live_allocations(int64_t *device, int64_t *pinned, int64_t *events) {
+    if (device) *device = g_live.device.load();
+    if (pinned) *pinned = g_live.pinned.load();
+    if (events) *events = g_live.events.load();
+    return AID_OK;
 }
 
 int aid_engine_config(const aid_engine *e, aid_config *out) {
@@ -349,14 +257,10 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
     hipStream_t s = pick_stream(e, stream);
     const int hop = e->cfg.hop;
 
-    // descriptors; host PCM is staged as one copy of the clips' span
-    if ((size_t)n_clips + 1 > e->h_desc_cap) {
-        if (e->h_desc) HIP_TRY(hipHostFree(e->h_desc));
-        e->h_desc = nullptr;
-        e->h_desc_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&e->h_desc, sizeof(ClipDesc) * ((size_t)n_clips + 1)));
-        e->h_desc_cap = (size_t)n_clips + 1;
-    }
+    // descriptors; host PCM is staged as one copy of the clips' span. h_desc is rewritten below, and may be
+    // reallocated here: the previous descriptor upload must have left it
+    HIP_TRY(e->desc_ev.wait());
+    HIP_TRY(e->h_desc.reserve((size_t)n_clips + 1));
     // a different stream than the previous call's: order against it the simple way
     if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
     // same clips, PCM location and strip length as the descriptors already on the device: no re-upload
@@ -366,11 +270,6 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
                      e->desc_key[2 * n_clips] == loc;
     for (int c = 0; desc_same && c < n_clips; ++c)
         desc_same = e->desc_key[2 * c] == offsets[c] && e->desc_key[2 * c + 1] == clip_len(c);
-    // h_desc is rewritten below: the previous descriptor upload must have left it
-    if (e->desc_ev_live) {
-        HIP_TRY(hipEventSynchronize(e->desc_ev));
-        e->desc_ev_live = false;
-    }
     e->clip_base.assign(n_clips, 0);
     e->clip_frames.assign(n_clips, 0);
     int64_t frames = 0, strips = 0, chunks = 0, recs = 0, staged = 0, kstrips = 0;
@@ -400,8 +299,8 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
     // (the words lag a few calls). Results never depend on the width or the strip length. At width 2 nothing exits on
     // the audio it is chosen for: 1 strip per slot (1.25: K2 0.111 against 0.093 ms).
     constexpr int kK2Hold = 64;
-    const uint64_t cw = e->h_cold ? *reinterpret_cast<volatile uint64_t *>(e->h_cold) : 0;
-    const uint64_t sw = e->h_cold ? *reinterpret_cast<volatile uint64_t *>(e->h_cold + 1) : 0;
+    const uint64_t cw = e->h_cold.p ? *reinterpret_cast<volatile uint64_t *>(e->h_cold.p) : 0;
+    const uint64_t sw = e->h_cold.p ? *reinterpret_cast<volatile uint64_t *>(e->h_cold.p + 1) : 0;
     const int seen_width = (sw >> 32) ? (int)((cw >> 32) / (sw >> 32)) : 0;  // of the launch that was counted
     int width = e->k2_width_force;
     if (!width) {
@@ -458,7 +357,7 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
     for (int c = 0, g = 0; c < n_clips; ++c) {
         const int64_t n = clip_len(c);
         const int64_t F = num_frames(n, hop);
-        ClipDesc &d = e->h_desc[c];
+        ClipDesc &d = e->h_desc.p[c];
         while (c == gstart[g + 1]) ++g;
         if (c == gstart[g]) gfirst[g] = frames;
         if (loc == AID_PCM_DEVICE) {
@@ -505,10 +404,10 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
         HIP_TRY(e->k2_cold.reserve(128));
         HIP_TRY(hipMemsetAsync(e->k2_cold.p, 0, 128 * sizeof(uint32_t), s));
     }
-    if (!e->h_cold) {
-        HIP_TRY(hipHostMalloc((void **)&e->h_cold, 2 * sizeof(uint64_t), hipHostMallocMapped));
-        e->h_cold[0] = e->h_cold[1] = 0;
-        HIP_TRY(hipHostGetDevicePointer((void **)&e->h_cold_dev, e->h_cold, 0));
+    if (!e->h_cold.p) {
+        HIP_TRY(e->h_cold.reserve(2, hipHostMallocMapped));
+        e->h_cold.p[0] = e->h_cold.p[1] = 0;
+        HIP_TRY(hipHostGetDevicePointer((void **)&e->h_cold_dev, e->h_cold.p, 0));
     }
     HIP_TRY(e->chunk_counts.reserve((size_t)chunks + 1));
     HIP_TRY(e->records.reserve((size_t)recs + 1));
@@ -517,8 +416,8 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
     if (loc == AID_PCM_HOST && staged > 0) {
         // K1 of an earlier call may still read the staging buffer: on the same stream the new copy is ordered after
         // it (a pipelined submit must not wait for the previous batch's K1), on another stream the host waits
-        if (e->stage_ev_live && e->stage_stream != s) HIP_TRY(hipEventSynchronize(e->stage_ev));
-        e->stage_ev_live = false;
+        if (e->stage_stream != s) HIP_TRY(e->stage_ev.wait());
+        e->stage_ev.live = false;
         // one copy of the clips' whole span (clips at odd offsets are read with dword-aligned float2 loads; a copy
         // per clip cost ~10-20 us of call overhead each: 64 coalesced service queries ~1 ms)
         // the staging buffer is raw bytes to both formats (s16: half the copy); stage_ev orders its reuse across them
@@ -528,10 +427,8 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
         dpcm = e->pcm_stage.p;
     }
     if (n_clips > 0 && !desc_same) {
-        if (!e->desc_ev) HIP_TRY(hipEventCreateWithFlags(&e->desc_ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(e->desc.p, e->h_desc, sizeof(ClipDesc) * n_clips, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(e->desc_ev, s));
-        e->desc_ev_live = true;
+        HIP_TRY(hipMemcpyAsync(e->desc.p, e->h_desc.p, sizeof(ClipDesc) * n_clips, hipMemcpyHostToDevice, s));
+        HIP_TRY(e->desc_ev.record(s));
         e->desc_key.resize(2 * (size_t)n_clips);
         for (int c = 0; c < n_clips; ++c) {
             e->desc_key[2 * c] = offsets[c];
@@ -557,14 +454,12 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
             if (gframes[g] == 0) continue;
             {
                 ProfScope ps(e, AID_K_STFT, s, true);
-                launch_stft_power(dpcm, fmt == kS16, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab,
+                launch_stft_power(dpcm, fmt == kS16, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab.p,
                                   e->power.p, false, e->hotw.p, e->cfg.peak_threshold,
                                   (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0, rel ? e->clip_qmax.p + ca : nullptr, s);
             }
             if (loc == AID_PCM_HOST && g == n_groups - 1) {
-                if (!e->stage_ev) HIP_TRY(hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(e->stage_ev, s));
-                e->stage_ev_live = true;
+                HIP_TRY(e->stage_ev.record(s));
                 e->stage_stream = s;
             }
             {
@@ -699,27 +594,24 @@ int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int6
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->own_stream;
     if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    float *d_pcm = nullptr, *d_out = nullptr;
-    ClipDesc *d_desc = nullptr;
+    DevBuf<float> d_pcm, d_out;
+    DevBuf<ClipDesc> d_desc;
     ClipDesc d{};
     d.frames = F;
-    HIP_TRY(hipMalloc(&d_pcm, n * sizeof(float)));
-    hipError_t he = hipMalloc(&d_out, F * kBins * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc(&d_desc, sizeof(ClipDesc));
-    if (he == hipSuccess) he = hipMemcpy(d_pcm, pcm, n * sizeof(float), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_desc, &d, sizeof(ClipDesc), hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        launch_stft_power(d_pcm, false, d_desc, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop, e->d_tab,
-                          d_out, true, nullptr, e->cfg.peak_threshold, true, nullptr, s);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(s);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, F * kBins * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_pcm);
-    (void)hipFree(d_out);
-    (void)hipFree(d_desc);
-    if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("aid_spectrogram: ") + hipGetErrorString(he));
-    return AID_OK;
+    HIP_TRY(d_pcm.reserve((size_t)n));
+    // from here every failure is AID_ERR_DEVICE under the function's name
+    auto ok = [](hipError_t he) {
+        return he == hipSuccess ? AID_OK : fail(AID_ERR_DEVICE, std::string("aid_spectrogram: ") + hipGetErrorString(he));
+    };
+    if (int rc = ok(d_out.reserve((size_t)(F * kBins)))) return rc;
+    if (int rc = ok(d_desc.reserve(1))) return rc;
+    if (int rc = ok(hipMemcpy(d_pcm.p, pcm, n * sizeof(float), hipMemcpyHostToDevice))) return rc;
+    if (int rc = ok(hipMemcpy(d_desc.p, &d, sizeof(ClipDesc), hipMemcpyHostToDevice))) return rc;
+    launch_stft_power(d_pcm.p, false, d_desc.p, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop,
+                      e->d_tab.p, d_out.p, true, nullptr, e->cfg.peak_threshold, true, nullptr, s);
+    if (int rc = ok(hipGetLastError())) return rc;
+    if (int rc = ok(hipStreamSynchronize(s))) return rc;
+    return ok(hipMemcpy(out, d_out.p, F * kBins * sizeof(float), hipMemcpyDeviceToHost));
 }
 
 int aid_synth_rate(aid_engine *e, float *dst, const uint32_t *tracks, const int64_t *starts, int32_t n_clips,
@@ -740,37 +632,26 @@ int aid_synth_rate(aid_engine *e, float *dst, const uint32_t *tracks, const int6
     if (e->last_stream && (!async || e->last_stream != s)) HIP_TRY(hipStreamSynchronize(e->last_stream));
     // the previous call's copies and kernel must have left the pinned staging and the device arrays before a
     // reserve may reallocate them or the copies below overwrite them
-    if (e->synth_ev_live) {
-        HIP_TRY(hipEventSynchronize(e->synth_ev));
-        e->synth_ev_live = false;
-    }
+    HIP_TRY(e->synth_ev.wait());
     HIP_TRY(e->synth_tracks.reserve(n_clips));
     HIP_TRY(e->synth_starts.reserve(n_clips));
     // tracks + starts go up from pinned staging (the caller's arrays may be gone when an async copy runs)
     const size_t tb = ((size_t)n_clips * sizeof(uint32_t) + 7) & ~(size_t)7, need = tb + (size_t)n_clips * sizeof(int64_t);
-    if (need > e->h_synth_cap) {
-        if (e->h_synth) HIP_TRY(hipHostFree(e->h_synth));
-        e->h_synth = nullptr;
-        e->h_synth_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&e->h_synth, need));
-        e->h_synth_cap = need;
-    }
-    std::memcpy(e->h_synth, tracks, (size_t)n_clips * sizeof(uint32_t));
-    std::memcpy(e->h_synth + tb, starts, (size_t)n_clips * sizeof(int64_t));
-    HIP_TRY(hipMemcpyAsync(e->synth_tracks.p, e->h_synth, n_clips * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->synth_starts.p, e->h_synth + tb, n_clips * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(e->h_synth.reserve(need));
+    std::memcpy(e->h_synth.p, tracks, (size_t)n_clips * sizeof(uint32_t));
+    std::memcpy(e->h_synth.p + tb, starts, (size_t)n_clips * sizeof(int64_t));
+    HIP_TRY(hipMemcpyAsync(e->synth_tracks.p, e->h_synth.p, n_clips * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->synth_starts.p, e->h_synth.p + tb, n_clips * sizeof(int64_t), hipMemcpyHostToDevice, s));
     {
         ProfScope ps(e, AID_K_SYNTH, s);
         launch_synth(dst, e->synth_tracks.p, e->synth_starts.p, n_clips, n, sample_rate, noise_a, salt, fmax_hz,
-                     !(flags & AID_SYNTH_STATIONARY), e->d_sin, s);
+                     !(flags & AID_SYNTH_STATIONARY), e->d_sin.p, s);
     }
     HIP_TRY(hipGetLastError());
     // the event covers the kernel's reads of synth_tracks / synth_starts as well as the copies into them, so the
     // next call (any stream) waits for both before it reuses the pinned staging or the device arrays; last_stream
     // makes every later call on another stream wait for this one too
-    if (!e->synth_ev) HIP_TRY(hipEventCreateWithFlags(&e->synth_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(e->synth_ev, s));
-    e->synth_ev_live = true;
+    HIP_TRY(e->synth_ev.record(s));
     e->last_stream = s;
     if (!async) HIP_TRY(hipStreamSynchronize(s));
     return AID_OK;
@@ -808,7 +689,7 @@ static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse,
     const std::pair<int32_t, int32_t> key{p.up, impulse ? -p.down : p.down};
     auto it = e->rs_taps.find(key);
     if (it != e->rs_taps.end()) {
-        *out = it->second;
+        *out = it->second.p;
         return AID_OK;
     }
     std::vector<float> h = resample_phase_taps(p);
@@ -816,15 +697,12 @@ static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse,
         std::fill(h.begin(), h.end(), 0.0f);
         h[(size_t)(p.hl % p.up) * p.J + p.hl / p.up] = 1.0f;  // taps[k], k = phase + j * up = hl
     }
-    float *taps = nullptr;
-    HIP_TRY(hipMalloc(&taps, h.size() * sizeof(float)));
-    hipError_t he = hipMemcpy(taps, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipFree(taps);
-        return fail(AID_ERR_DEVICE, std::string("aid_resample: ") + hipGetErrorString(he));
-    }
-    e->rs_taps[key] = taps;
-    *out = taps;
+    DevBuf<float> taps;
+    HIP_TRY(taps.reserve(h.size()));
+    hipError_t he = hipMemcpy(taps.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("aid_resample: ") + hipGetErrorString(he));
+    *out = taps.p;
+    e->rs_taps[key] = std::move(taps);
     return AID_OK;
 }
 
@@ -935,26 +813,6 @@ int aid_resample_s16(aid_engine *e, const int16_t *src, int64_t n, int32_t chann
     return resample_whole(e, src, kS16, n, channels, sr_in, sr_out, dst, cap, n_out, stream);
 }
 
-}  // extern "C"
-
-// grow a device buffer to hold `want` elements, keeping the first `keep` (stream-ordered copy)
-template <typename T>
-static int grow_keep(DevBuf<T> &b, size_t keep, size_t want, hipStream_t s) {
-    if (want <= b.n) return AID_OK;
-    size_t cap = std::max(want, b.n * 2);
-    T *p = nullptr;
-    HIP_TRY(hipMalloc(&p, cap * sizeof(T)));
-    keep = b.p ? std::min(keep, b.n) : 0;  // nothing stored yet on the first growth
-    if (keep) HIP_TRY(hipMemcpyAsync(p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (b.p) (void)hipFree(b.p);
-    b.p = p;
-    b.n = cap;
-    return AID_OK;
-}
-
-extern "C" {
-
 int aid_dedup_reset(aid_engine *e) {
     if (!e) return fail(AID_ERR_INVALID, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
@@ -987,9 +845,9 @@ int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, 
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->own_stream;
     if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    if (int rc = grow_keep(e->dd_words, (size_t)e->dd_nw, (size_t)(e->dd_nw + nw + 1), s)) return rc;
-    if (int rc = grow_keep(e->dd_off, (size_t)e->dd_n + 1, (size_t)(e->dd_n + n + 1), s)) return rc;
-    if (int rc = grow_keep(e->dd_dur, (size_t)e->dd_n, (size_t)(e->dd_n + n), s)) return rc;
+    HIP_TRY(e->dd_words.grow_keep((size_t)e->dd_nw, (size_t)(e->dd_nw + nw + 1), s));
+    HIP_TRY(e->dd_off.grow_keep((size_t)e->dd_n + 1, (size_t)(e->dd_n + n + 1), s));
+    HIP_TRY(e->dd_dur.grow_keep((size_t)e->dd_n, (size_t)(e->dd_n + n), s));
     std::vector<int64_t> off(n + 1);
     for (int32_t i = 0; i <= n; ++i) off[i] = e->dd_nw + offsets[i];
     if (nw > 0) HIP_TRY(hipMemcpyAsync(e->dd_words.p + e->dd_nw, words, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -1173,25 +1031,16 @@ int aid_profile_read(aid_engine *e, double *ms, int64_t *launches, int32_t reset
 
 // ---------------------------------------------------------------- index
 
-static int grow_copy_u32(DevBuf<uint32_t> &b, size_t keep, size_t want, hipStream_t s) {
-    if (want <= b.n) return AID_OK;
-    size_t cap = std::max(want, b.n * 2);
-    uint32_t *p = nullptr;
-    HIP_TRY(hipMalloc(&p, cap * sizeof(uint32_t)));
-    if (keep) HIP_TRY(hipMemcpyAsync(p, b.p, keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (b.p) (void)hipFree(b.p);
-    b.p = p;
-    b.n = cap;
+// the three posting planes grown to `want` postings, every stored posting kept
+static int grow_postings(aid_engine *e, size_t want, hipStream_t s) {
+    HIP_TRY(e->p_hash.grow_keep((size_t)e->n_post, want, s));
+    HIP_TRY(e->p_track.grow_keep((size_t)e->n_post, want, s));
+    HIP_TRY(e->p_t.grow_keep((size_t)e->n_post, want, s));
     return AID_OK;
 }
 
 static int reserve_postings(aid_engine *e, int64_t extra, hipStream_t s) {
-    const size_t want = (size_t)(e->n_post + extra);
-    if (int rc = grow_copy_u32(e->p_hash, e->n_post, want, s)) return rc;
-    if (int rc = grow_copy_u32(e->p_track, e->n_post, want, s)) return rc;
-    if (int rc = grow_copy_u32(e->p_t, e->n_post, want, s)) return rc;
-    return AID_OK;
+    return grow_postings(e, (size_t)(e->n_post + extra), s);
 }
 
 // wait for the engine's own streams (not the whole device: torch streams, other engines and ranks on the
@@ -1214,13 +1063,9 @@ static int reserve_tracks(aid_engine *e, uint32_t max_track_plus1, hipStream_t s
         // synchronous: the engine's tombstones must be whole in the new buffer before it replaces the old one
         hipError_t he = hipMemcpyAsync(nb.p, e->h_tomb.data(), e->n_tracks, hipMemcpyHostToDevice, s);
         if (he == hipSuccess) he = hipStreamSynchronize(s);
-        if (he != hipSuccess) {
-            nb.release();
-            return fail(AID_ERR_DEVICE, std::string("reserve_tracks: ") + hipGetErrorString(he));
-        }
+        if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("reserve_tracks: ") + hipGetErrorString(he));
     }
-    std::swap(e->tomb, nb);
-    nb.release();
+    std::swap(e->tomb, nb);  // nb frees the old buffer
     return AID_OK;
 }
 
@@ -1237,10 +1082,9 @@ static int ensure_tracks(aid_engine *e, uint32_t max_track_plus1, hipStream_t s)
 // the posting count of the last aid_index_add_extracted, if still in flight, made exact (the append's own
 // kernels are ordered before the event; a reader of n_post or of the planes calls this first)
 static int settle_postings(aid_engine *e) {
-    if (!e->add_live) return AID_OK;
-    HIP_TRY(hipEventSynchronize(e->add_ev));
-    e->add_live = false;
-    if (e->post_pend) e->n_post = *e->h_npost;
+    if (!e->add_ev.live) return AID_OK;
+    HIP_TRY(e->add_ev.wait());
+    if (e->post_pend) e->n_post = *e->h_npost.p;
     e->post_pend = false;
     return AID_OK;
 }
@@ -1272,15 +1116,8 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     // pinned staging, whose H2D copies precede that call's event
     if (int rc = settle_postings(e)) return rc;
     // pinned staging [counts n][src n][dst n][tracks n/2+1] (int64 slots)
-    const size_t need = 3 * (size_t)n + (size_t)n / 2 + 1;
-    if (need > e->h_stage_cap) {
-        if (e->h_stage) HIP_TRY(hipHostFree(e->h_stage));
-        e->h_stage = nullptr;
-        e->h_stage_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&e->h_stage, need * sizeof(int64_t)));
-        e->h_stage_cap = need;
-    }
-    int64_t *counts = e->h_stage, *src = counts + n, *dst = src + n;
+    HIP_TRY(e->h_stage.reserve(3 * (size_t)n + (size_t)n / 2 + 1));
+    int64_t *counts = e->h_stage.p, *src = counts + n, *dst = src + n;
     uint32_t *trk = reinterpret_cast<uint32_t *>(dst + n);
     uint32_t mx = 0;
     for (int c = 0; c < n; ++c) {
@@ -1299,19 +1136,18 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     // O(log n) times), unless that headroom would take more than a quarter of the free device memory
     const int64_t bound = e->total_records;
     const int64_t cap = (int64_t)std::min({e->p_hash.n, e->p_track.n, e->p_t.n});
-    if (!e->add_ev) HIP_TRY(hipEventCreateWithFlags(&e->add_ev, hipEventDisableTiming));
     if (e->n_post + bound <= cap) {
-        if (!e->h_npost) HIP_TRY(hipHostMalloc((void **)&e->h_npost, sizeof(int64_t)));
+        HIP_TRY(e->h_npost.reserve(1));
         HIP_TRY(e->d_npost.reserve(1));
         HIP_TRY(hipMemcpyAsync(e->x_src.p, src, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(e->x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         launch_append_offsets(e->counts.p, n, e->n_post, e->x_dst.p, e->d_npost.p, s);
         launch_records_to_postings(e->records.p, e->x_src.p, e->counts.p, e->x_dst.p, e->x_tracks.p, n, e->p_hash.p,
                                    e->p_track.p, e->p_t.p, s);
-        HIP_TRY(hipMemcpyAsync(e->h_npost, e->d_npost.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(e->add_ev, s));
+        HIP_TRY(hipMemcpyAsync(e->h_npost.p, e->d_npost.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e->add_ev.record(s));
         HIP_TRY(hipGetLastError());
-        e->add_live = e->post_pend = true;
+        e->post_pend = true;
     } else {
         HIP_TRY(hipMemcpyAsync(counts, e->counts.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -1329,9 +1165,8 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
         HIP_TRY(hipMemcpyAsync(e->x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         launch_records_to_postings(e->records.p, e->x_src.p, e->counts.p, e->x_dst.p, e->x_tracks.p, n, e->p_hash.p,
                                    e->p_track.p, e->p_t.p, s);
-        HIP_TRY(hipEventRecord(e->add_ev, s));  // the staging's copies (the next call waits for them)
+        HIP_TRY(e->add_ev.record(s));  // the staging's copies (the next call waits for them)
         HIP_TRY(hipGetLastError());  // no sync: every reader of the posting planes syncs last_stream first
-        e->add_live = true;
         e->n_post += tot;
     }
     e->index_dirty = true;
@@ -1405,13 +1240,7 @@ int aid_index_compact(aid_engine *e, int64_t *n_removed) {
     hipStream_t s = e->own_stream;
     if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
     const int64_t nb = (e->n_post + 1023) / 1024;
-    DevBuf<uint32_t> cnt, off, tmp, nh, ntr, nt;
-    struct Release {  // every scratch buffer goes on every return path
-        DevBuf<uint32_t> *b[6];
-        ~Release() {
-            for (auto *x : b) x->release();
-        }
-    } release_all{{&cnt, &off, &tmp, &nh, &ntr, &nt}};
+    DevBuf<uint32_t> cnt, off, tmp, nh, ntr, nt;  // scratch: freed on every return path
     HIP_TRY(cnt.reserve((size_t)nb));
     HIP_TRY(off.reserve((size_t)nb));
     HIP_TRY(tmp.reserve(4 * ((size_t)nb / 1024 + 2) + 4096));
@@ -1643,9 +1472,7 @@ static int splice_reserve_locked(aid_engine *e, int64_t first, int64_t tot, uint
     if (tot < 0) return fail(AID_ERR_INVALID, "index exchange: negative posting count");
     if (first + tot > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index exchange: more than 2^32 postings");
     const size_t want = (size_t)std::max<int64_t>(first + tot, e->n_post);
-    if (int rc = grow_copy_u32(e->p_hash, e->n_post, want, s)) return rc;
-    if (int rc = grow_copy_u32(e->p_track, e->n_post, want, s)) return rc;
-    if (int rc = grow_copy_u32(e->p_t, e->n_post, want, s)) return rc;
+    if (int rc = grow_postings(e, want, s)) return rc;
     return n_tracks > e->n_tracks ? reserve_tracks(e, n_tracks, s) : AID_OK;
 }
 
@@ -1928,12 +1755,6 @@ int aid_index_load(aid_engine *e, const char *path) {
     HIP_TRY(hipSetDevice(e->device));
     if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
     DevBuf<uint32_t> cols[3];
-    struct Release {
-        DevBuf<uint32_t> *c;
-        ~Release() {
-            for (int i = 0; i < 3; ++i) c[i].release();
-        }
-    } release_cols{cols};
     std::vector<uint32_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(n, 1), 1 << 24));
     for (int c = 0; c < 3; ++c) {
         HIP_TRY(cols[c].reserve((size_t)std::max<int64_t>(n, 1)));
@@ -1946,10 +1767,6 @@ int aid_index_load(aid_engine *e, const char *path) {
     std::vector<uint8_t> tomb(nt);
     if (nt && std::fread(tomb.data(), 1, nt, f) != nt) return fail(AID_ERR_INVALID, "truncated index file");
     DevBuf<uint8_t> dtomb;
-    struct ReleaseTomb {
-        DevBuf<uint8_t> *b;
-        ~ReleaseTomb() { b->release(); }
-    } release_tomb{&dtomb};
     HIP_TRY(dtomb.reserve(std::max<size_t>(nt, 1024)));
     if (nt) HIP_TRY(hipMemcpy(dtomb.p, tomb.data(), nt, hipMemcpyHostToDevice));
     // commit: swap the new planes in (the old ones are released with the scratch)

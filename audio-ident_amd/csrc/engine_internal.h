@@ -6,11 +6,13 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/aidfp.h"
+#include "aidfp_buffers.h"
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
 #include "aidfp_layout.h"
@@ -30,64 +32,12 @@ int fail(int code, const std::string &msg);  // engine.cpp: keeps msg for aid_la
                         std::string(#expr) + ": " + hipGetErrorString(_e));                        \
     } while (0)
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;  // capacity in elements
-    hipError_t reserve(size_t want) {
-        if (want <= n) return hipSuccess;
-        if (p) {  // growing: in-flight work of earlier calls may still use the old buffer
-            (void)hipDeviceSynchronize();
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        n = 0;
-        size_t cap = std::max(want, (size_t)1);
-        hipError_t e = hipMalloc(&p, cap * sizeof(T));
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// page-locked host buffer (hipHostMalloc): device-to-host copies into it are asynchronous, so a call can queue its
-// result copies behind its kernels and wait once
-template <typename T>
-struct HostBuf {
-    T *p = nullptr;
-    size_t n = 0;  // capacity in elements
-    hipError_t reserve(size_t want) {  // callers have synchronised any copy still targeting the old buffer
-        if (want <= n) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t cap = std::max(want, (size_t)64);
-        hipError_t e = hipHostMalloc((void **)&p, cap * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 // K5's page-locked result block: a call queues the copies into it behind its kernels and waits once. The engine
 // owns one (the synchronous calls), every aid_query_ticket its own
 struct K5Host {
     HostBuf<int64_t> meta;   // [0, nq) record starts, [nq, 2nq) record counts, [2nq, 3nq) exact votes
     HostBuf<int32_t> rows;   // the LDS pass's rows, [nq][max_results][5]
     HostBuf<int32_t> nrows;  // the LDS pass's row counts; -r: handed back for reason r (index.hip)
-    void release() {
-        meta.release();
-        rows.release();
-        nrows.release();
-    }
 };
 
 struct ProfEvent {
@@ -95,12 +45,37 @@ struct ProfEvent {
     hipEvent_t a, b;
 };
 
+// the engine's own stream. Declared ahead of every buffer and event of aid_engine, so it is destroyed after them
+struct OwnStream {
+    hipStream_t s = nullptr;
+    OwnStream() = default;
+    OwnStream(const OwnStream &) = delete;
+    OwnStream &operator=(const OwnStream &) = delete;
+    ~OwnStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
+
+// asynchronous windowed query (query.cpp): the ticket owns page-locked result buffers and a device
+// copy of its records (the next submit reuses the engine's extraction buffers in stream order), so a query the LDS
+// path hands back can still be answered on the global path at collect time
+struct aid_query_ticket {
+    int nq = 0;
+    int64_t nrec = 0;
+    hipStream_t s = nullptr;
+    Event ev;
+    K5Host host;  // the LDS pass's results, complete behind ev
+    DevBuf<uint64_t> recs;
+    DevBuf<int64_t> qsc;  // device record starts and counts of the ticket's queries ([0, nq), [nq, 2nq))
+};
+
 struct aid_engine {
     aid_config cfg{};
     int device = 0;
-    hipStream_t own_stream = nullptr;
-    Tables *d_tab = nullptr;
-    int16_t *d_sin = nullptr;
+    OwnStream own_stream;
+    DevBuf<Tables> d_tab;
+    DevBuf<int16_t> d_sin;
 
     DevBuf<float> pcm_stage;
     DevBuf<float> power;
@@ -112,7 +87,7 @@ struct aid_engine {
     DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3
     // pinned, host-mapped, two words: K3 stores (cold waves | waves << 32) and (twice-walked strips | strips << 32) of
     // the last K2 here; waves / strips is the width that K2 ran at
-    uint64_t *h_cold = nullptr;
+    HostBuf<uint64_t> h_cold;
     uint64_t *h_cold_dev = nullptr;  // its device address
     int k2_width_force = 0;          // aid_engine_force K2_WIDTH: 2 or 4 quarter waves per K2 workgroup; 0 = adaptive
     int k2_width = 4;                // the adaptive choice (extract_locked); also the width of the last call
@@ -124,10 +99,8 @@ struct aid_engine {
     DevBuf<int64_t> counts;
     DevBuf<uint32_t> synth_tracks;
     DevBuf<int64_t> synth_starts;
-    uint8_t *h_synth = nullptr;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
-    size_t h_synth_cap = 0;
-    hipEvent_t synth_ev = nullptr;
-    bool synth_ev_live = false;
+    HostBuf<uint8_t> h_synth;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
+    Event synth_ev;
 
     // index (FPSPEC 7): all postings (SoA source of truth) + the CSR built from them
     DevBuf<uint32_t> p_hash, p_track, p_t;
@@ -135,9 +108,9 @@ struct aid_engine {
     // aid_index_add_extracted appends without waiting for its clips' counts: K_append scans them on the device and
     // the new total comes back to pinned h_npost behind add_ev; settle_postings() makes n_post exact again
     DevBuf<int64_t> d_npost;
-    int64_t *h_npost = nullptr;
-    hipEvent_t add_ev = nullptr;  // after the last append's staging copies (and, if post_pend, its count copy)
-    bool add_live = false, post_pend = false;
+    HostBuf<int64_t> h_npost;
+    Event add_ev;  // after the last append's staging copies (and, if post_pend, its count copy)
+    bool post_pend = false;
     std::vector<uint8_t> h_tomb;  // per track id: 1 = removed
     DevBuf<uint8_t> tomb;
     uint32_t n_tracks = 0;        // max track id + 1
@@ -166,7 +139,8 @@ struct aid_engine {
     DevBuf<uint64_t> q_ranges;  // K5: per query record its CSR range (k_query_votes -> k_match_lds)
     K5Host k5h;                 // run_queries: the synchronous calls' result block
     HostBuf<int64_t> hq_start;  // the queries' record starts (clip_base) staged page-locked for their upload
-    std::vector<aid_query_ticket *> ticket_pool;  // collected tickets, reused: their buffers and event stay allocated
+    // collected tickets, reused: their buffers and event stay allocated
+    std::vector<std::unique_ptr<aid_query_ticket>> ticket_pool;
     DevBuf<int64_t> q_votes;  // exact votes per query (LDS-histogram eligibility)
     DevBuf<int64_t> x_src, x_dst;
     // batched exact lane (aid_exact_lane): PCM staging, window descriptors, consensus output
@@ -175,7 +149,7 @@ struct aid_engine {
     DevBuf<int32_t> x_order, x_clipwin, x_nout;
     DevBuf<double> x_out;  // aid_exact_row, 3 x 8 bytes each
     DevBuf<int64_t> g_meta;            // all-gather: (count, n_tracks) per rank
-    std::map<std::pair<int32_t, int32_t>, float *> rs_taps;  // (up, down) -> device [up][J] taps
+    std::map<std::pair<int32_t, int32_t>, DevBuf<float>> rs_taps;  // (up, down) -> device [up][J] taps
     // Chromaprint dedup catalog (insertion order) + scan scratch
     DevBuf<uint32_t> dd_words;
     DevBuf<int64_t> dd_off;
@@ -189,14 +163,11 @@ struct aid_engine {
     DevBuf<uint32_t> x_tracks;
     size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
 
-    int64_t *h_stage = nullptr;  // pinned staging of aid_index_add_extracted
-    size_t h_stage_cap = 0;
-    ClipDesc *h_desc = nullptr;  // pinned
-    size_t h_desc_cap = 0;
+    HostBuf<int64_t> h_stage;  // pinned staging of aid_index_add_extracted
+    HostBuf<ClipDesc> h_desc;  // pinned
     // extraction call hazards, tracked with events instead of a stream sync per call:
     // h_desc is the source of an async H2D copy; pcm_stage is read by K1
-    hipEvent_t desc_ev = nullptr, stage_ev = nullptr;
-    bool desc_ev_live = false, stage_ev_live = false;
+    Event desc_ev, stage_ev;
     hipStream_t stage_stream = nullptr;  // the stream whose K1 read pcm_stage last
     std::vector<int64_t> desc_key;  // offsets (+ pcm location) the device descriptors were built for
     ClipDesc *desc_dev_for_key = nullptr;
@@ -229,6 +200,14 @@ struct aid_engine {
     double prof_ms[AID_K_COUNT] = {};
     int64_t prof_n[AID_K_COUNT] = {};
     std::mutex mu;
+
+    ~aid_engine() {  // the profiling events; every other resource is a member that frees itself
+        for (auto &p : pending) {
+            event_destroy(p.a);
+            event_destroy(p.b);
+        }
+        for (hipEvent_t ev : pool) event_destroy(ev);
+    }
 };
 
 static inline hipEvent_t take_event(aid_engine *e) {
@@ -238,7 +217,7 @@ static inline hipEvent_t take_event(aid_engine *e) {
         return ev;
     }
     hipEvent_t ev = nullptr;
-    if (hipEventCreate(&ev) != hipSuccess) return nullptr;
+    if (event_create(&ev, hipEventDefault) != hipSuccess) return nullptr;
     return ev;
 }
 
@@ -316,12 +295,11 @@ static inline int check_clips(const char *fn, aid_engine *e, const void *pcm, co
     return AID_OK;
 }
 
-// engine lock held, all three; defined among their file's extern "C" functions, hence the linkage
+// engine lock held, both; defined among engine.cpp's extern "C" functions, hence the linkage
 extern "C" {
 int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                   void *stream, const int64_t *ends = nullptr);  // engine.cpp
-int ensure_index(aid_engine *e);       // engine.cpp: (re)builds the CSR if postings changed since the last build
-void free_ticket_pool(aid_engine *e);  // query.cpp
+                   void *stream, const int64_t *ends = nullptr);
+int ensure_index(aid_engine *e);  // (re)builds the CSR if postings changed since the last build
 }  // extern "C"
 
 #pragma GCC visibility pop

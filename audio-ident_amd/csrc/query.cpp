@@ -289,35 +289,12 @@ int aid_query_pcm_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets,
 }
 
 // ---- asynchronous windowed query: submit enqueues the extraction, K5's LDS path and the result
-// copies and returns; collect waits for the ticket's event. The ticket owns page-locked result buffers and a device copy
-// of its records (the next submit reuses the engine's extraction buffers in stream order), so a query the LDS path
-// hands back can still be answered on the global path at collect time.
-struct aid_query_ticket {
-    int nq = 0;
-    int64_t nrec = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    K5Host host;  // the LDS pass's results, complete behind ev
-    DevBuf<uint64_t> recs;
-    DevBuf<int64_t> qsc;    // device record starts and counts of the ticket's queries ([0, nq), [nq, 2nq))
-    ~aid_query_ticket() {
-        if (ev) (void)hipEventDestroy(ev);
-        host.release();
-        recs.release();
-        qsc.release();
-    }
-};
-
-void free_ticket_pool(aid_engine *e) {
-    for (aid_query_ticket *t : e->ticket_pool) delete t;
-    e->ticket_pool.clear();
-}
-
-static aid_query_ticket *take_ticket(aid_engine *e) {
-    // a pooled ticket keeps its page-locked and device buffers and its event: allocating them per call (hipHostMalloc,
-    // hipMalloc, and the hipFree that synchronises the device on release) had cost more than the overlap gained
-    if (e->ticket_pool.empty()) return new aid_query_ticket();
-    aid_query_ticket *t = e->ticket_pool.back();
+// copies and returns; collect waits for the ticket's event (struct aid_query_ticket: engine_internal.h).
+static std::unique_ptr<aid_query_ticket> take_ticket(aid_engine *e) {
+    // a pooled ticket keeps its page-locked and device buffers and its event: allocating them per call (pinned and
+    // device blocks, and the free that synchronises the device on release) had cost more than the overlap gained
+    if (e->ticket_pool.empty()) return std::unique_ptr<aid_query_ticket>(new aid_query_ticket());
+    std::unique_ptr<aid_query_ticket> t = std::move(e->ticket_pool.back());
     e->ticket_pool.pop_back();
     return t;
 }
@@ -347,8 +324,7 @@ static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64
     HIP_TRY(hipMemcpyAsync(t->recs.p, e->records.p, (size_t)t->nrec * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     // always the LDS pass: a ticket ignores the K5_PATH force (collect runs the global path for what it hands back)
     if (int rc = k5_enqueue(e, t->recs.p, t->qsc.p, t->qsc.p + nq, nq, t->nrec, true, true, t->host, s, true)) return rc;
-    if (!t->ev) HIP_TRY(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(t->ev, s));
+    HIP_TRY(t->ev.record(s));
     return AID_OK;
 }
 
@@ -360,7 +336,7 @@ static int windows_submit_entry(const char *fn, aid_engine *e, const void *pcm, 
     for (int c = 0; c < n_windows; ++c)
         if (starts[c] < 0 || ends[c] < starts[c]) return fail(AID_ERR_INVALID, std::string(fn) + ": bad window");
     std::lock_guard<std::mutex> lk(e->mu);
-    std::unique_ptr<aid_query_ticket> t(take_ticket(e));
+    std::unique_ptr<aid_query_ticket> t = take_ticket(e);
     if (int rc = submit_locked(e, pcm, fmt, starts, ends, n_windows, AID_PCM_DEVICE, stream, t.get())) return rc;
     *out = t.release();
     return AID_OK;
@@ -385,7 +361,7 @@ static int pcm_submit_entry(const char *fn, aid_engine *e, const void *pcm, PcmF
     *out = nullptr;
     if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
-    std::unique_ptr<aid_query_ticket> t(take_ticket(e));
+    std::unique_ptr<aid_query_ticket> t = take_ticket(e);
     if (int rc = submit_locked(e, pcm, fmt, offsets, nullptr, n_clips, loc, stream, t.get()))
         return drain_host_copy(e, loc, stream, rc);
     *out = t.release();
@@ -408,13 +384,13 @@ extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid
         return fail(AID_ERR_INVALID, "aid_query_windows_collect: bad argument");
     }
     if (t->nq > 0 && (!rows || !nrows)) {
-        if (t->ev) (void)hipEventSynchronize(t->ev);
+        (void)t->ev.wait();
         std::lock_guard<std::mutex> lk(e->mu);
-        e->ticket_pool.push_back(t);
+        e->ticket_pool.emplace_back(t);
         return fail(AID_ERR_INVALID, "aid_query_windows_collect: bad argument");
     }
     if (t->nq > 0) {
-        const hipError_t we = hipEventSynchronize(t->ev);
+        const hipError_t we = t->ev.wait();
         if (we != hipSuccess) {
             delete t;
             return fail(AID_ERR_DEVICE, std::string("aid_query_windows_collect: ") + hipGetErrorString(we));
@@ -424,7 +400,7 @@ extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid
     struct Back {  // back to the pool on every return below (the ticket's work has completed)
         aid_engine *e;
         aid_query_ticket *t;
-        ~Back() { e->ticket_pool.push_back(t); }
+        ~Back() { e->ticket_pool.emplace_back(t); }
     } back{e, t};
     if (t->nq == 0) return AID_OK;
     const int nq = t->nq, mr = e->cfg.max_results;

@@ -409,55 +409,6 @@ __global__ __launch_bounds__(256) void k_vec_gather(const float4 *__restrict__ s
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 
-template <typename T>
-hipError_t VecBuf<T>::reserve(size_t want) {
-    if (want <= n) return hipSuccess;
-    if (p) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p);
-    }
-    p = nullptr;
-    n = 0;
-    const size_t cap = std::max(want, (size_t)64);
-    hipError_t e = hipMalloc((void **)&p, cap * sizeof(T));
-    if (e == hipSuccess) n = cap;
-    return e;
-}
-template <typename T>
-void VecBuf<T>::release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-}
-
-void VecCatalog::release_all() {
-    if (d_vecs) (void)hipFree(d_vecs);
-    d_vecs = nullptr;
-    cap_rows = 0;
-    d_track.release();
-    d_off.release();
-    d_dead.release();
-    d_raw.release();
-    d_q.release();
-    d_scores.release();
-    d_keys0.release();
-    d_keys1.release();
-    d_cand.release();
-    d_smax.release();
-    d_thr.release();
-    d_ccnt.release();
-    d_hentry.release();
-    d_htrack.release();
-    d_excl.release();
-    d_hscore.release();
-    d_hoff.release();
-    d_nhits.release();
-    d_cnt.release();
-    d_nout.release();
-    d_start.release();
-    d_rows.release();
-}
-
 static int vfail(VecCatalog &c, int code, const std::string &msg) {
     c.err = msg;
     return code;
@@ -475,13 +426,12 @@ static bool vec_dim_ok(int dim) { return dim >= 32 && dim <= 1024 && dim % 32 ==
 
 int vec_reset(VecCatalog &c, int dim) {
     if (!vec_dim_ok(dim)) return vfail(c, AID_ERR_INVALID, "aid_vec_reset: dim must be a multiple of 32 in [32, 1024]");
-    if (dim != c.dim && c.d_vecs) {  // another row size: the stored tiles are of no use
+    if (dim != c.dim && c.d_vecs.p) {  // another row size: the stored tiles are of no use
         (void)hipDeviceSynchronize();
-        (void)hipFree(c.d_vecs);
-        c.d_vecs = nullptr;
+        c.d_vecs.release();
         c.cap_rows = 0;
     }
-    if (c.d_vecs) VEC_TRY(hipMemset(c.d_vecs, 0, (size_t)c.cap_rows * dim * sizeof(float)));
+    if (c.d_vecs.p) VEC_TRY(hipMemset(c.d_vecs.p, 0, (size_t)c.cap_rows * dim * sizeof(float)));
     c.dim = dim;
     c.n = c.n_live = 0;
     c.h_track.clear();
@@ -496,22 +446,16 @@ static int vec_grow(VecCatalog &c, int64_t rows, hipStream_t s) {
     if (rows > c.cap_rows) {
         int64_t cap = std::max<int64_t>(rows, c.cap_rows * 2);
         cap = (cap + 1023) / 1024 * 1024;
-        float *p = nullptr;
-        VEC_TRY(hipMalloc((void **)&p, (size_t)cap * c.dim * sizeof(float)));
+        // the new block is whole (stored tiles copied, the rest +0) before it replaces the old one: a failure on
+        // the way leaves the catalog as it was (DevBuf::grow_keep would commit ahead of the memset)
+        DevBuf<float> nb;
+        VEC_TRY(nb.reserve((size_t)cap * c.dim));
         const size_t keep = (size_t)((c.n + 31) / 32) * 32 * c.dim;
-        hipError_t e = hipSuccess;
-        if (keep) e = hipMemcpyAsync(p, c.d_vecs, keep * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(p + keep, 0, ((size_t)cap * c.dim - keep) * sizeof(float), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            VEC_TRY(e);
-        }
-        if (c.d_vecs) {
-            (void)hipDeviceSynchronize();
-            (void)hipFree(c.d_vecs);
-        }
-        c.d_vecs = p;
+        if (keep) VEC_TRY(hipMemcpyAsync(nb.p, c.d_vecs.p, keep * sizeof(float), hipMemcpyDeviceToDevice, s));
+        VEC_TRY(hipMemsetAsync(nb.p + keep, 0, ((size_t)cap * c.dim - keep) * sizeof(float), s));
+        VEC_TRY(hipStreamSynchronize(s));
+        if (c.d_vecs.p) (void)hipDeviceSynchronize();
+        std::swap(c.d_vecs, nb);  // nb frees the old block
         c.cap_rows = cap;
     }
     if ((size_t)rows > c.d_track.n) {  // payload columns: rebuilt from the host mirror
@@ -561,7 +505,7 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
         VEC_TRY(hipMemcpyAsync(c.d_raw.p, vecs, (size_t)n * c.dim * sizeof(float), hipMemcpyHostToDevice, s));
         src = c.d_raw.p;
     }
-    hipLaunchKernelGGL(k_vec_normalize, dim3((unsigned)n), dim3(64), 0, s, src, n, c.dim, c.d_vecs, c.n);
+    hipLaunchKernelGGL(k_vec_normalize, dim3((unsigned)n), dim3(64), 0, s, src, n, c.dim, c.d_vecs.p, c.n);
     VEC_TRY(hipGetLastError());
     VEC_TRY(hipMemcpyAsync(c.d_track.p + c.n, tr.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     VEC_TRY(hipMemcpyAsync(c.d_off.p + c.n, of.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
@@ -599,24 +543,19 @@ int vec_compact(VecCatalog &c, int64_t *n_removed, hipStream_t s) {
     for (int64_t i = 0; i < c.n; ++i)
         if (!c.h_dead[i]) map.push_back((uint32_t)i);
     const int64_t m = (int64_t)map.size();
-    float *p = nullptr;
-    VEC_TRY(hipMalloc((void **)&p, (size_t)c.cap_rows * c.dim * sizeof(float)));
-    hipError_t e = c.d_hentry.reserve((size_t)std::max<int64_t>(m, 1));
-    if (e == hipSuccess && m) e = hipMemcpyAsync(c.d_hentry.p, map.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
+    {
+        DevBuf<float> nb;  // the live rows gathered into a new block, which then replaces the old one
+        VEC_TRY(nb.reserve((size_t)c.cap_rows * c.dim));
+        VEC_TRY(c.d_hentry.reserve((size_t)std::max<int64_t>(m, 1)));
+        if (m) VEC_TRY(hipMemcpyAsync(c.d_hentry.p, map.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         const int64_t f4 = c.cap_rows * (c.dim / 4);
         hipLaunchKernelGGL(k_vec_gather, dim3((unsigned)((f4 + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<const float4 *>(c.d_vecs), c.d_hentry.p, m, c.cap_rows, c.dim,
-                           reinterpret_cast<float4 *>(p));
-        e = hipGetLastError();
+                           reinterpret_cast<const float4 *>(c.d_vecs.p), c.d_hentry.p, m, c.cap_rows, c.dim,
+                           reinterpret_cast<float4 *>(nb.p));
+        VEC_TRY(hipGetLastError());
+        VEC_TRY(hipStreamSynchronize(s));
+        std::swap(c.d_vecs, nb);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        VEC_TRY(e);
-    }
-    (void)hipFree(c.d_vecs);
-    c.d_vecs = p;
     for (int64_t r = 0; r < m; ++r) {
         c.h_track[r] = c.h_track[map[r]];
         c.h_chunk[r] = c.h_chunk[map[r]];
@@ -652,7 +591,7 @@ static int vec_scan_batch(VecCatalog &c, const float *dq, int nb, hipStream_t s)
     hipLaunchKernelGGL(k_vec_normalize, dim3((unsigned)nb), dim3(64), 0, s, dq, (int64_t)nb, dim, c.d_q.p,
                        (int64_t)0);
     if (c.force_path == 2) {
-        hipLaunchKernelGGL(k_vec_scan_valu, dim3((unsigned)((ns + 255) / 256), (unsigned)nb), dim3(256), 0, s, c.d_vecs, ns,
+        hipLaunchKernelGGL(k_vec_scan_valu, dim3((unsigned)((ns + 255) / 256), (unsigned)nb), dim3(256), 0, s, c.d_vecs.p, ns,
                            c.d_q.p, dim, c.d_scores.p);
     } else {
         const int chunk = c.force_chunk ? c.force_chunk : kVecScanChunk;
@@ -662,7 +601,7 @@ static int vec_scan_batch(VecCatalog &c, const float *dq, int nb, hipStream_t s)
         if (lds > 65536)
             VEC_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vec_scan_mfma<512>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_vec_scan_mfma<512>, dim3(gx, (unsigned)nqt), dim3(512), lds, s, c.d_vecs, n_tiles, tiles_per_wg,
+        hipLaunchKernelGGL(k_vec_scan_mfma<512>, dim3(gx, (unsigned)nqt), dim3(512), lds, s, c.d_vecs.p, n_tiles, tiles_per_wg,
                            c.d_q.p, dim, c.d_scores.p, ns);
     }
     VEC_TRY(hipGetLastError());
@@ -922,7 +861,7 @@ int vec_save(VecCatalog &c, const char *path, hipStream_t s) {
     const size_t nf = (size_t)((c.n + 31) / 32) * 32 * c.dim;
     std::vector<float> v(nf);
     if (nf) {
-        VEC_TRY(hipMemcpyAsync(v.data(), c.d_vecs, nf * sizeof(float), hipMemcpyDeviceToHost, s));
+        VEC_TRY(hipMemcpyAsync(v.data(), c.d_vecs.p, nf * sizeof(float), hipMemcpyDeviceToHost, s));
         VEC_TRY(hipStreamSynchronize(s));
     }
     FILE *f = fopen(path, "wb");
@@ -975,7 +914,7 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
     if (int rc = vec_reset(c, h.dim)) return rc;
     if (h.n == 0) return AID_OK;
     if (int rc = vec_grow(c, h.n, s)) return rc;
-    VEC_TRY(hipMemcpyAsync(c.d_vecs, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    VEC_TRY(hipMemcpyAsync(c.d_vecs.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, s));
     VEC_TRY(hipMemcpyAsync(c.d_track.p, tr.data(), tr.size() * 4, hipMemcpyHostToDevice, s));
     VEC_TRY(hipMemcpyAsync(c.d_off.p, of.data(), of.size() * 8, hipMemcpyHostToDevice, s));
     VEC_TRY(hipMemcpyAsync(c.d_dead.p, dead.data(), dead.size(), hipMemcpyHostToDevice, s));

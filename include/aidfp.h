@@ -492,6 +492,10 @@ int aid_profile_enable(aid_engine *e, int32_t on);
 int aid_profile_select(aid_engine *e, uint32_t kernel_mask);
 /* ms[AID_K_COUNT] summed device time, launches[AID_K_COUNT]; synchronises; reset != 0 clears. */
 int aid_profile_read(aid_engine *e, double *ms, int64_t *launches, int32_t reset);
+/* Diagnostic: how many device blocks, page-locked host blocks and events the library's engines (their tickets
+   included) hold in this process right now; any pointer may be NULL. A destroyed engine leaves all three as they
+   were before it was created. */
+int aid_live_allocations(int64_t *device, int64_t *pinned, int64_t *events);
 
 #ifdef __cplusplus
 }
