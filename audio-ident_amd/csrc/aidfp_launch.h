@@ -37,15 +37,13 @@ void launch_index_count(const uint32_t *ph, const uint32_t *ptrack, int64_t n, c
 void launch_index_scatter(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n,
                           const uint8_t *tomb, uint32_t n_tracks, uint32_t *cursor, uint64_t *post, hipStream_t s);
 void launch_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t s);
-size_t index_sort_temp_bytes(int64_t n);
-bool k4_ab_sort_built();
 int match_lds_blocks_per_cu();
 size_t radix_scratch_u32(int64_t n);
 hipError_t launch_index_sort_build(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n,
                                    const uint8_t *tomb, uint32_t n_tracks, uint32_t *keys0, uint32_t *keys1,
-                                   uint64_t *vals0, uint64_t *vals1, void *temp, size_t temp_bytes, bool use_rocprim,
-                                   uint32_t *scratch, uint32_t *E, uint32_t *offsets, unsigned long long *nz,
-                                   uint64_t **vals_out, uint16_t *sig, int rank_mode, hipStream_t s);
+                                   uint64_t *vals0, uint64_t *vals1, uint32_t *scratch, uint32_t *E, uint32_t *offsets,
+                                   unsigned long long *nz, uint64_t **vals_out, uint16_t *sig, int rank_mode,
+                                   hipStream_t s);
 void launch_make_sig(const uint64_t *post, int64_t n, uint16_t *sig, hipStream_t s);
 void launch_compact(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n, const uint8_t *tomb,
                     uint32_t n_tracks, uint32_t *cnt, uint32_t *off, uint32_t *tmp, uint32_t *oh, uint32_t *otrack,

@@ -3,20 +3,14 @@
 // Owns one GPU's tables and workspaces, builds the per-call clip descriptors
 // (one small H2D copy), launches K1..K3 on the caller's stream and exposes the
 // results. Replaces the `olaf_c` process boundary of the reference
-// (audio-ident-service/app/audio/fingerprint.py:87-270). The query half (K5, the query entry points, the exact
-// lane) is query.cpp; engine_internal.h holds what the two files share.
+// (audio-ident-service/app/audio/fingerprint.py:87-270). The hash index is index_host.cpp, its exchange between ranks
+// index_exchange.cpp, the query half (K5, the query entry points, the exact lane) query.cpp; engine_internal.h holds
+// what the host files share.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
 #include "engine_internal.h"
 #include "resample_design.h"
@@ -37,6 +31,8 @@ int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+
+const std::string &last_error_text() { return g_err; }
 
 
 static void build_tables(Tables &t) {
@@ -188,18 +184,15 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
             e->k2_width_force = value;
             return AID_OK;
         case AID_FORCE_K4_BUILD:
-            if (value < 0 || value > 4)
-                return fail(AID_ERR_INVALID, "K4_BUILD: 0 default, 1 radix, 2 atomic, 3 rocPRIM, 4 radix with ballot ranks");
-            if (value == 3 && !k4_ab_sort_built())
-                return fail(AID_ERR_INVALID, "K4_BUILD 3: the rocPRIM A/B build is only in the diagnostic variant "
-                                             "library (build_ext.build(variant=\"k4rocprim\"), -DAID_K4_ROCPRIM_AB)");
-            e->k4_mode = value == 2 ? 0 : value == 3 ? 1 : 2;
-            e->k4_rank = value == 4 ? 1 : 0;
-            e->index_dirty = true;
+            if (value < 0 || value > 4 || value == 3)  // 3 was a library sort kept for A/B; the number stays retired
+                return fail(AID_ERR_INVALID, "K4_BUILD: 0 default, 1 radix, 2 atomic, 4 radix with ballot ranks");
+            e->idx.k4_build = value == 2 ? K4Build::kAtomic : K4Build::kRadix;
+            e->idx.k4_rank = value == 4 ? 1 : 0;
+            e->idx.csr_current = false;
             return AID_OK;
         case AID_FORCE_EXCHANGE_FAIL:
             if (value != 0 && value != 1) return fail(AID_ERR_INVALID, "EXCHANGE_FAIL: 0 or 1");
-            e->inject_exchange_fail = value;
+            e->idx.inject_exchange_fail = value;
             return AID_OK;
         case AID_FORCE_LANE_GATHER:
             if (value != 0 && value != 1) return fail(AID_ERR_INVALID, "LANE_GATHER: 0 or 1");
@@ -590,10 +583,9 @@ int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int6
     const int64_t F = num_frames(n, e->cfg.hop);
     if (F * kBins > cap) return fail(AID_ERR_INVALID, "output capacity too small");
     if (F == 0) return AID_OK;
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    EngineCall call(e, nullptr, false, kDrainLast);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     DevBuf<float> d_pcm, d_out;
     DevBuf<ClipDesc> d_desc;
     ClipDesc d{};
@@ -841,10 +833,9 @@ int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, 
     if (int rc = check_offsets(offsets, n, "aid_dedup_add")) return rc;
     const int64_t nw = offsets[n];
     if (nw > 0 && !words) return fail(AID_ERR_INVALID, "aid_dedup_add: null words");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    EngineCall call(e, nullptr, false, kDrainLast);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     HIP_TRY(e->dd_words.grow_keep((size_t)e->dd_nw, (size_t)(e->dd_nw + nw + 1), s));
     HIP_TRY(e->dd_off.grow_keep((size_t)e->dd_n + 1, (size_t)(e->dd_n + n + 1), s));
     HIP_TRY(e->dd_dur.grow_keep((size_t)e->dd_n, (size_t)(e->dd_n + n), s));
@@ -867,10 +858,9 @@ int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets,
     if (int rc = check_offsets(offsets, nq, "aid_dedup_scan")) return rc;
     const int64_t nw = offsets[nq];
     if (nw > 0 && !words) return fail(AID_ERR_INVALID, "aid_dedup_scan: null words");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    EngineCall call(e, nullptr, false, kDrainLast);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     const int nc = std::max(1, dedup_chunks(e->dd_n));
     std::vector<double> lo(nq), hi(nq);
     for (int32_t q = 0; q < nq; ++q) {  // the reference's SQL bounds (dedup.py:193-194)
@@ -909,9 +899,9 @@ int aid_dedup_pairs(aid_engine *e, const uint32_t *a, const int64_t *a_off, cons
     if (int rc = check_offsets(b_off, n, "aid_dedup_pairs")) return rc;
     const int64_t na = a_off[n], nb = b_off[n];
     if ((na > 0 && !a) || (nb > 0 && !b)) return fail(AID_ERR_INVALID, "aid_dedup_pairs: null words");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
+    EngineCall call(e);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
     HIP_TRY(e->dq_words.reserve((size_t)na + 1));
     HIP_TRY(e->dq_words2.reserve((size_t)nb + 1));
     HIP_TRY(e->dq_off.reserve((size_t)n + 1));
@@ -929,16 +919,14 @@ int aid_dedup_pairs(aid_engine *e, const uint32_t *a, const int64_t *a_off, cons
 }
 
 // ---- vector lane (FPSPEC 9): thin wrappers over csrc/vector.hip, one critical section per call
-#define VEC_CALL(e, stream, call)                                                   \
-    do {                                                                            \
-        if (!(e)) return fail(AID_ERR_INVALID, "null engine");                      \
-        std::lock_guard<std::mutex> lk((e)->mu);                                    \
-        HIP_TRY(hipSetDevice((e)->device));                                         \
-        if ((e)->last_stream) HIP_TRY(hipStreamSynchronize((e)->last_stream));      \
-        hipStream_t s = (stream) ? (hipStream_t)(stream) : (e)->own_stream;         \
-        (void)s;                                                                    \
-        const int rc = (call);                                                      \
-        return rc ? fail(rc, (e)->vec.err) : AID_OK;                                \
+#define VEC_CALL(e, stream, call)                      \
+    do {                                               \
+        EngineCall ec(e, stream, false, kDrainLast);   \
+        if (ec.rc) return ec.rc;                       \
+        hipStream_t s = ec.s;                          \
+        (void)s;                                       \
+        const int rc = (call);                         \
+        return rc ? fail(rc, (e)->vec.err) : AID_OK;   \
     } while (0)
 
 int aid_vec_reset(aid_engine *e, int32_t dim) { VEC_CALL(e, nullptr, vec_reset(e->vec, dim)); }
@@ -1027,326 +1015,6 @@ int aid_profile_read(aid_engine *e, double *ms, int64_t *launches, int32_t reset
     return AID_OK;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- index
-
-// the three posting planes grown to `want` postings, every stored posting kept
-static int grow_postings(aid_engine *e, size_t want, hipStream_t s) {
-    HIP_TRY(e->p_hash.grow_keep((size_t)e->n_post, want, s));
-    HIP_TRY(e->p_track.grow_keep((size_t)e->n_post, want, s));
-    HIP_TRY(e->p_t.grow_keep((size_t)e->n_post, want, s));
-    return AID_OK;
-}
-
-static int reserve_postings(aid_engine *e, int64_t extra, hipStream_t s) {
-    return grow_postings(e, (size_t)(e->n_post + extra), s);
-}
-
-// wait for the engine's own streams (not the whole device: torch streams, other engines and ranks on the
-// same GPU keep running) before a buffer that in-flight engine work may read is freed
-static void sync_engine_streams(aid_engine *e, hipStream_t s) {
-    if (e->last_stream && e->last_stream != s) (void)hipStreamSynchronize(e->last_stream);
-    if (e->own_stream && e->own_stream != s) (void)hipStreamSynchronize(e->own_stream);
-    (void)hipStreamSynchronize(s);
-}
-
-// capacity of the track tables for max_track_plus1 ids, without changing the index: the new tombstone
-// buffer is allocated (and filled) before the old one goes, so a failed growth leaves the engine as it was
-static int reserve_tracks(aid_engine *e, uint32_t max_track_plus1, hipStream_t s) {
-    const size_t want = std::max<size_t>(max_track_plus1, 1024);
-    if (want <= e->tomb.n) return AID_OK;
-    DevBuf<uint8_t> nb;
-    HIP_TRY(nb.reserve(std::max(want, 2 * e->tomb.n)));
-    if (e->tomb.p) sync_engine_streams(e, s);  // in-flight queries may still read the old tombstones
-    if (e->n_tracks) {
-        // synchronous: the engine's tombstones must be whole in the new buffer before it replaces the old one
-        hipError_t he = hipMemcpyAsync(nb.p, e->h_tomb.data(), e->n_tracks, hipMemcpyHostToDevice, s);
-        if (he == hipSuccess) he = hipStreamSynchronize(s);
-        if (he != hipSuccess) return fail(AID_ERR_DEVICE, std::string("reserve_tracks: ") + hipGetErrorString(he));
-    }
-    std::swap(e->tomb, nb);  // nb frees the old buffer
-    return AID_OK;
-}
-
-// grow the track tables to max_track_plus1 ids (reserve first: nothing changes if that fails)
-static int ensure_tracks(aid_engine *e, uint32_t max_track_plus1, hipStream_t s) {
-    if (max_track_plus1 <= e->n_tracks) return AID_OK;
-    if (int rc = reserve_tracks(e, max_track_plus1, s)) return rc;
-    e->h_tomb.resize(max_track_plus1, 0);
-    e->n_tracks = max_track_plus1;
-    HIP_TRY(hipMemcpyAsync(e->tomb.p, e->h_tomb.data(), e->n_tracks, hipMemcpyHostToDevice, s));
-    return AID_OK;
-}
-
-// the posting count of the last aid_index_add_extracted, if still in flight, made exact (the append's own
-// kernels are ordered before the event; a reader of n_post or of the planes calls this first)
-static int settle_postings(aid_engine *e) {
-    if (!e->add_ev.live) return AID_OK;
-    HIP_TRY(e->add_ev.wait());
-    if (e->post_pend) e->n_post = *e->h_npost.p;
-    e->post_pend = false;
-    return AID_OK;
-}
-
-extern "C" {
-
-int aid_index_reset(aid_engine *e) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    e->n_post = 0;
-    e->n_tracks = 0;
-    e->h_tomb.clear();
-    e->index_built = false;
-    e->index_dirty = true;
-    e->n_indexed = 0;
-    return AID_OK;
-}
-
-int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
-    if (!e || (!track_ids && e->n_clips > 0)) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad argument");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction to index");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
-    const int n = e->n_clips;
-    if (n == 0) return AID_OK;
-    // the previous call's count (normally long arrived: this batch's extraction was queued behind it) and its
-    // pinned staging, whose H2D copies precede that call's event
-    if (int rc = settle_postings(e)) return rc;
-    // pinned staging [counts n][src n][dst n][tracks n/2+1] (int64 slots)
-    HIP_TRY(e->h_stage.reserve(3 * (size_t)n + (size_t)n / 2 + 1));
-    int64_t *counts = e->h_stage.p, *src = counts + n, *dst = src + n;
-    uint32_t *trk = reinterpret_cast<uint32_t *>(dst + n);
-    uint32_t mx = 0;
-    for (int c = 0; c < n; ++c) {
-        src[c] = e->clip_base[c];
-        trk[c] = track_ids[c];
-        mx = std::max(mx, track_ids[c] + 1);
-    }
-    if (int rc = ensure_tracks(e, mx, s)) return rc;
-    HIP_TRY(e->x_src.reserve(n));
-    HIP_TRY(e->x_dst.reserve(n));
-    HIP_TRY(e->x_tracks.reserve(n));
-    // the batch's postings are at most its hash capacity: when the planes hold that much more, the append is
-    // scanned on the device and nothing waits for it; otherwise the counts come back first and the planes grow
-    // to the exact need plus one batch's hash capacity (1.5x the records buffer the extraction already holds),
-    // so the following appends of such batches are asynchronous again (growth doubles: this path runs
-    // O(log n) times), unless that headroom would take more than a quarter of the free device memory
-    const int64_t bound = e->total_records;
-    const int64_t cap = (int64_t)std::min({e->p_hash.n, e->p_track.n, e->p_t.n});
-    if (e->n_post + bound <= cap) {
-        HIP_TRY(e->h_npost.reserve(1));
-        HIP_TRY(e->d_npost.reserve(1));
-        HIP_TRY(hipMemcpyAsync(e->x_src.p, src, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(e->x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        launch_append_offsets(e->counts.p, n, e->n_post, e->x_dst.p, e->d_npost.p, s);
-        launch_records_to_postings(e->records.p, e->x_src.p, e->counts.p, e->x_dst.p, e->x_tracks.p, n, e->p_hash.p,
-                                   e->p_track.p, e->p_t.p, s);
-        HIP_TRY(hipMemcpyAsync(e->h_npost.p, e->d_npost.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(e->add_ev.record(s));
-        HIP_TRY(hipGetLastError());
-        e->post_pend = true;
-    } else {
-        HIP_TRY(hipMemcpyAsync(counts, e->counts.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        int64_t tot = 0;
-        for (int c = 0; c < n; ++c) {
-            dst[c] = e->n_post + tot;
-            tot += counts[c];
-        }
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const bool room = (size_t)bound * 3 * sizeof(uint32_t) <= free_b / 4;
-        if (int rc = reserve_postings(e, tot + (room ? bound : 0), s)) return rc;
-        HIP_TRY(hipMemcpyAsync(e->x_src.p, src, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(e->x_dst.p, dst, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(e->x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        launch_records_to_postings(e->records.p, e->x_src.p, e->counts.p, e->x_dst.p, e->x_tracks.p, n, e->p_hash.p,
-                                   e->p_track.p, e->p_t.p, s);
-        HIP_TRY(e->add_ev.record(s));  // the staging's copies (the next call waits for them)
-        HIP_TRY(hipGetLastError());  // no sync: every reader of the posting planes syncs last_stream first
-        e->n_post += tot;
-    }
-    e->index_dirty = true;
-    return AID_OK;
-}
-
-int aid_index_add_postings(aid_engine *e, const uint32_t *hash, const uint32_t *track, const uint32_t *t, int64_t n,
-                           int32_t location) {
-    if (!e || n < 0 || (n > 0 && (!hash || !track || !t))) return fail(AID_ERR_INVALID, "aid_index_add_postings: bad argument");
-    if (location != AID_PCM_HOST && location != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "bad location");
-    if (n == 0) return AID_OK;
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (int rc = settle_postings(e)) return rc;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    uint32_t mx = 0;
-    if (location == AID_PCM_HOST) {
-        for (int64_t i = 0; i < n; ++i) mx = std::max(mx, track[i] + 1);
-    } else {
-        // device track ids: one max-reduction via a host copy of the track column
-        std::vector<uint32_t> tr(n);
-        HIP_TRY(hipMemcpy(tr.data(), track, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < n; ++i) mx = std::max(mx, tr[i] + 1);
-    }
-    if (int rc = reserve_postings(e, n, s)) return rc;
-    if (int rc = ensure_tracks(e, mx, s)) return rc;
-    const hipMemcpyKind k = location == AID_PCM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIP_TRY(hipMemcpyAsync(e->p_hash.p + e->n_post, hash, n * sizeof(uint32_t), k, s));
-    HIP_TRY(hipMemcpyAsync(e->p_track.p + e->n_post, track, n * sizeof(uint32_t), k, s));
-    HIP_TRY(hipMemcpyAsync(e->p_t.p + e->n_post, t, n * sizeof(uint32_t), k, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    e->n_post += n;
-    e->index_dirty = true;
-    return AID_OK;
-}
-
-int aid_index_add_track(aid_engine *e, uint32_t track) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (track == 0xFFFFFFFFu) return fail(AID_ERR_INVALID, "aid_index_add_track: bad track id");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    if (int rc = ensure_tracks(e, track + 1, s)) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return AID_OK;
-}
-
-int aid_index_remove(aid_engine *e, uint32_t track) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (track >= e->n_tracks || e->h_tomb[track]) return fail(AID_ERR_INVALID, "track not indexed");
-    HIP_TRY(hipSetDevice(e->device));
-    e->h_tomb[track] = 1;
-    ++e->tomb_since_build;  // the CSR still holds its postings until the next finalize
-    HIP_TRY(hipMemcpy(e->tomb.p + track, &e->h_tomb[track], 1, hipMemcpyHostToDevice));
-    return AID_OK;
-}
-
-int aid_index_compact(aid_engine *e, int64_t *n_removed) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    if (n_removed) *n_removed = 0;
-    bool any = false;
-    for (uint8_t t : e->h_tomb) any = any || t;
-    if (!any || e->n_post == 0) return AID_OK;
-    if (e->n_post > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index holds more than 2^32 postings");
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    const int64_t nb = (e->n_post + 1023) / 1024;
-    DevBuf<uint32_t> cnt, off, tmp, nh, ntr, nt;  // scratch: freed on every return path
-    HIP_TRY(cnt.reserve((size_t)nb));
-    HIP_TRY(off.reserve((size_t)nb));
-    HIP_TRY(tmp.reserve(4 * ((size_t)nb / 1024 + 2) + 4096));
-    HIP_TRY(nh.reserve((size_t)e->n_post));
-    HIP_TRY(ntr.reserve((size_t)e->n_post));
-    HIP_TRY(nt.reserve((size_t)e->n_post));
-    launch_compact(e->p_hash.p, e->p_track.p, e->p_t.p, e->n_post, e->tomb.p, e->n_tracks, cnt.p, off.p, tmp.p, nh.p,
-                   ntr.p, nt.p, s);
-    HIP_TRY(hipGetLastError());
-    uint32_t last_off = 0, last_cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&last_off, off.p + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&last_cnt, cnt.p + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const int64_t live = (int64_t)last_off + last_cnt;
-    if (n_removed) *n_removed = e->n_post - live;
-    std::swap(e->p_hash, nh);
-    std::swap(e->p_track, ntr);
-    std::swap(e->p_t, nt);  // the old planes are released with the scratch buffers
-    e->n_post = live;  // tombstones stay: removed ids are never reused, and the CSR skips nothing new
-    e->index_dirty = true;
-    return AID_OK;
-}
-
-static int finalize_locked(aid_engine *e) {
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = settle_postings(e)) return rc;
-    hipStream_t s = e->own_stream;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    if (e->n_post > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index holds more than 2^32 postings");
-    const size_t K = (size_t)index_keys() + 1;
-    HIP_TRY(e->idx_cnt.reserve(K));
-    HIP_TRY(e->idx_off.reserve(K));
-    HIP_TRY(e->scan_tmp.reserve(4 * (K / 1024 + 2) + 4096));
-    HIP_TRY(e->idx_post.reserve((size_t)std::max<int64_t>(e->n_post, 1)));
-    // + 8: K5's LDS path reads the signatures in aligned chunks of 4 or 8; a record's last chunk may reach past the end
-    HIP_TRY(e->idx_sig.reserve((size_t)std::max<int64_t>(e->n_post, 1) + 8));
-    if (e->n_tracks == 0) HIP_TRY(e->tomb.reserve(1024));
-    HIP_TRY(hipMemsetAsync(e->idx_cnt.p, 0, K * sizeof(uint32_t), s));
-    HIP_TRY(e->nz.reserve(1));
-    HIP_TRY(hipMemsetAsync(e->nz.p, 0, sizeof(unsigned long long), s));
-    if (e->k4_mode >= 1 && e->n_post > 0) {
-        // sort build (index_sort.hip): stable radix sort of (key27, track | t << 32) -> run ends -> max-scan
-        const size_t np = (size_t)e->n_post;
-        const bool rocprim_ab = e->k4_mode == 1;
-        size_t tb = 0;
-        if (rocprim_ab) {
-            tb = index_sort_temp_bytes(e->n_post);
-            if (tb == 0) return fail(AID_ERR_DEVICE, "radix sort: temporary storage query failed");
-            HIP_TRY(e->srt_tmp.reserve(tb));
-        }
-        HIP_TRY(e->srt_scratch.reserve(radix_scratch_u32(e->n_post)));
-        HIP_TRY(e->srt_k0.reserve(np));
-        HIP_TRY(e->srt_k1.reserve(np));
-        HIP_TRY(e->srt_v.reserve(np));
-        uint64_t *sorted = nullptr;
-        {
-            ProfScope ps(e, AID_K_INDEX_BUILD, s);
-            bool any_removed = false;
-            for (uint8_t t : e->h_tomb) any_removed = any_removed || t;
-            HIP_TRY(launch_index_sort_build(e->p_hash.p, e->p_track.p, e->p_t.p, e->n_post,
-                                            any_removed ? e->tomb.p : nullptr, e->n_tracks,
-                                            e->srt_k0.p, e->srt_k1.p, e->srt_v.p, e->idx_post.p, e->srt_tmp.p, tb,
-                                            rocprim_ab, e->srt_scratch.p, e->idx_cnt.p, e->idx_off.p, e->nz.p, &sorted,
-                                            e->idx_sig.p, e->k4_rank, s));
-            if (sorted == e->srt_v.p) std::swap(e->srt_v, e->idx_post);  // the CSR's post array is where the sort ended
-        }
-    } else {
-        launch_index_count(e->p_hash.p, e->p_track.p, e->n_post, e->tomb.p, e->n_tracks, e->idx_cnt.p, s);
-        launch_count_nonzero(e->idx_cnt.p, (int64_t)K, e->nz.p, s);
-        launch_scan(e->idx_cnt.p, e->idx_off.p, (int64_t)K, e->scan_tmp.p, s);
-        HIP_TRY(hipMemcpyAsync(e->idx_cnt.p, e->idx_off.p, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        launch_index_scatter(e->p_hash.p, e->p_track.p, e->p_t.p, e->n_post, e->tomb.p, e->n_tracks, e->idx_cnt.p,
-                             e->idx_post.p, s);
-        launch_make_sig(e->idx_post.p, e->n_post, e->idx_sig.p, s);  // (only the first n_indexed are read)
-    }
-    HIP_TRY(hipGetLastError());
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, e->idx_off.p + (K - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    e->n_indexed = total;
-    e->index_built = true;
-    e->index_dirty = false;
-    e->tomb_since_build = 0;  // the build skipped every removed track's postings
-    // the sort's double buffers are 16 B per posting (15 GB at the 100k-track catalog): kept for the next build
-    // of a small index (a store + query cycle rebuilds it), released above 1 GiB
-    if ((e->srt_k0.n + e->srt_k1.n) * 4 + e->srt_v.n * 8 + e->srt_tmp.n + e->srt_scratch.n * 4 > ((size_t)1 << 30)) {
-        e->srt_k0.release();
-        e->srt_k1.release();
-        e->srt_v.release();
-        e->srt_tmp.release();
-        e->srt_scratch.release();
-    }
-    return AID_OK;
-}
-
-int ensure_index(aid_engine *e) {
-    if (e->index_dirty || !e->index_built) return finalize_locked(e);
-    return AID_OK;
-}
-
-int aid_index_finalize(aid_engine *e) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    return finalize_locked(e);
-}
-
 int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
     if (!e || (n > 0 && !out)) return fail(AID_ERR_INVALID, "aid_match_stats: bad argument");
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1359,427 +1027,6 @@ int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
         e->st_queries = e->st_votes = e->st_post_reads = e->st_q_lds = e->st_q_global = e->st_records = e->st_sig_reads = 0;
         for (auto &r : e->st_fb_reason) r = 0;
     }
-    return AID_OK;
-}
-
-int aid_index_stats(aid_engine *e, int64_t *n_postings, int64_t *n_live, uint32_t *n_tracks) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    if (n_postings) *n_postings = e->n_post;
-    if (n_live) *n_live = e->index_built && !e->index_dirty ? e->n_indexed : -1;
-    if (n_tracks) *n_tracks = e->n_tracks;
-    return AID_OK;
-}
-
-}  // extern "C"
-
-struct aid_comm {
-    ncclComm_t comm = nullptr;
-    int world = 0, rank = 0, device = -1;
-};
-
-#define NCCL_TRY(expr)                                                                              \
-    do {                                                                                            \
-        ncclResult_t r_ = (expr);                                                                   \
-        if (r_ != ncclSuccess) return fail(AID_ERR_DEVICE, std::string(#expr ": ") + ncclGetErrorString(r_)); \
-    } while (0)
-
-extern "C" {
-
-int aid_comm_id(uint8_t id[AID_COMM_ID_BYTES]) {
-    if (!id) return fail(AID_ERR_INVALID, "null id");
-    ncclUniqueId u;
-    NCCL_TRY(ncclGetUniqueId(&u));
-    static_assert(sizeof(u.internal) == AID_COMM_ID_BYTES, "RCCL unique id size");
-    std::memcpy(id, u.internal, AID_COMM_ID_BYTES);
-    return AID_OK;
-}
-
-int aid_comm_create(aid_engine *e, const uint8_t id[AID_COMM_ID_BYTES], int32_t world, int32_t rank, aid_comm **out) {
-    if (!e || !id || !out || world <= 0 || rank < 0 || rank >= world) return fail(AID_ERR_INVALID, "aid_comm_create: bad argument");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(e->device));
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIP_TRY(e->g_meta.reserve(2 * (size_t)world + 2));  // the exchange's (count, n_tracks) and ok rounds
-    }
-    ncclUniqueId u;
-    std::memcpy(u.internal, id, AID_COMM_ID_BYTES);
-    ncclComm_t c = nullptr;
-    NCCL_TRY(ncclCommInitRank(&c, world, u, rank));
-    aid_comm *ac = new aid_comm();
-    ac->comm = c;
-    ac->world = world;
-    ac->rank = rank;
-    ac->device = e->device;
-    *out = ac;
-    return AID_OK;
-}
-
-void aid_comm_destroy(aid_comm *c) {
-    if (!c) return;
-    if (c->comm) {
-        (void)hipSetDevice(c->device);
-        (void)ncclCommDestroy(c->comm);
-    }
-    delete c;
-}
-
-int aid_comm_size(const aid_comm *c, int32_t *world, int32_t *rank) {
-    if (!c || !c->comm) return fail(AID_ERR_INVALID, "aid_comm_size: null comm");
-    int n = 0, r = 0;
-    NCCL_TRY(ncclCommCount(c->comm, &n));
-    NCCL_TRY(ncclCommUserRank(c->comm, &r));
-    if (world) *world = n;
-    if (rank) *rank = r;
-    return AID_OK;
-}
-
-// the exchange in three steps (aid_index_allgather runs them around two RCCL all-gathers; a host-driven
-// exchange, e.g. torch.distributed over gloo, runs them around its own collectives)
-static int shard_info_locked(aid_engine *e, int64_t first, int64_t *count, uint32_t *n_tracks) {
-    if (int rc = settle_postings(e)) return rc;
-    if (first < 0 || first > e->n_post) return fail(AID_ERR_INVALID, "index exchange: first out of range");
-    *count = e->n_post - first;
-    *n_tracks = e->n_tracks;
-    return AID_OK;
-}
-
-static int pack_locked(aid_engine *e, int64_t first, uint32_t *planes, int64_t stride, hipStream_t s) {
-    if (e->inject_exchange_fail) {  // test hook: this rank's prepare step fails as a device OOM would
-        e->inject_exchange_fail = 0;
-        return fail(AID_ERR_NOMEM, "index exchange: injected failure of this rank's pack (aid_engine_force)");
-    }
-    if (int rc = settle_postings(e)) return rc;
-    const int64_t n = e->n_post - first;
-    if (n > stride) return fail(AID_ERR_INVALID, "aid_index_pack: stride below the shard's count");
-    const uint32_t *src[3] = {e->p_hash.p, e->p_track.p, e->p_t.p};
-    for (int q = 0; q < 3 && n > 0; ++q)
-        HIP_TRY(hipMemcpyAsync(planes + q * stride, src[q] + first, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    if (stride > n)  // padding: defined bytes on the wire
-        for (int q = 0; q < 3; ++q)
-            HIP_TRY(hipMemsetAsync(planes + q * stride + n, 0, (stride - n) * sizeof(uint32_t), s));
-    return AID_OK;
-}
-
-// everything a splice of `tot` postings at `first` (and n_tracks ids) can fail on, done before the exchange:
-// the posting planes and the tombstone buffer grow keeping every stored posting (n_post, not first) and
-// every tombstone; the index itself (n_post, n_tracks, the CSR) does not change
-static int splice_reserve_locked(aid_engine *e, int64_t first, int64_t tot, uint32_t n_tracks, hipStream_t s) {
-    if (int rc = settle_postings(e)) return rc;
-    if (first < 0 || first > e->n_post) return fail(AID_ERR_INVALID, "index exchange: first out of range");
-    if (tot < 0) return fail(AID_ERR_INVALID, "index exchange: negative posting count");
-    if (first + tot > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index exchange: more than 2^32 postings");
-    const size_t want = (size_t)std::max<int64_t>(first + tot, e->n_post);
-    if (int rc = grow_postings(e, want, s)) return rc;
-    return n_tracks > e->n_tracks ? reserve_tracks(e, n_tracks, s) : AID_OK;
-}
-
-// failure-atomic: everything that can fail (growth of the posting planes and track tables) happens before
-// the index changes; the union then replaces [first, n_post) in one stream-ordered pass
-static int splice_locked(aid_engine *e, int64_t first, const uint32_t *recv, int32_t world, int64_t stride,
-                         const int64_t *counts, uint32_t n_tracks, hipStream_t s) {
-    if (int rc = settle_postings(e)) return rc;
-    if (first < 0 || first > e->n_post) return fail(AID_ERR_INVALID, "aid_index_splice: first out of range");
-    int64_t tot = 0;
-    for (int r = 0; r < world; ++r) {
-        if (counts[r] < 0 || counts[r] > stride) return fail(AID_ERR_INVALID, "aid_index_splice: bad count");
-        tot += counts[r];
-    }
-    if (int rc = splice_reserve_locked(e, first, tot, n_tracks, s)) return rc;
-    if (int rc = ensure_tracks(e, n_tracks, s)) return rc;  // capacity reserved: only the commit is left
-    uint32_t *dst[3] = {e->p_hash.p, e->p_track.p, e->p_t.p};
-    int64_t at = first;
-    for (int r = 0; r < world; ++r) {
-        const int64_t n = counts[r];
-        for (int q = 0; q < 3 && n > 0; ++q)
-            HIP_TRY(hipMemcpyAsync(dst[q] + at, recv + ((size_t)r * 3 + q) * stride, n * sizeof(uint32_t),
-                                   hipMemcpyDeviceToDevice, s));
-        at += n;
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    e->n_post = at;
-    e->index_dirty = true;
-    return AID_OK;
-}
-
-int aid_index_shard_info(aid_engine *e, int64_t first, int64_t *count, uint32_t *n_tracks) {
-    if (!e || !count || !n_tracks) return fail(AID_ERR_INVALID, "aid_index_shard_info: null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    return shard_info_locked(e, first, count, n_tracks);
-}
-
-int aid_index_reserve(aid_engine *e, int64_t first, int64_t total, uint32_t n_tracks, void *stream) {
-    if (!e) return fail(AID_ERR_INVALID, "aid_index_reserve: null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = pick_stream(e, stream);
-    if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    return splice_reserve_locked(e, first, total, n_tracks, s);
-}
-
-int aid_index_pack(aid_engine *e, int64_t first, uint32_t *planes, int64_t stride, void *stream) {
-    if (!e || (!planes && stride > 0) || stride < 0) return fail(AID_ERR_INVALID, "aid_index_pack: bad argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    if (first < 0 || first > e->n_post) return fail(AID_ERR_INVALID, "aid_index_pack: first out of range");
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = pick_stream(e, stream);
-    if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    if (int rc = pack_locked(e, first, planes, stride, s)) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return AID_OK;
-}
-
-int aid_index_splice(aid_engine *e, int64_t first, const uint32_t *recv, int32_t world, int64_t stride,
-                     const int64_t *counts, uint32_t n_tracks, void *stream) {
-    if (!e || world <= 0 || stride < 0 || !counts || (!recv && stride > 0))
-        return fail(AID_ERR_INVALID, "aid_index_splice: bad argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = pick_stream(e, stream);
-    if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    return splice_locked(e, first, recv, world, stride, counts, n_tracks, s);
-}
-
-// one all-gather of an int64 pair per rank over the engine's meta buffer (reserved by aid_comm_create);
-// every rank calls it the same number of times, whatever its own state
-static int allgather_pair(aid_engine *e, aid_comm *c, int64_t a, int64_t b, std::vector<int64_t> &out, hipStream_t s) {
-    const int W = c->world;
-    const int64_t mine[2] = {a, b};
-    HIP_TRY(hipMemcpyAsync(e->g_meta.p, mine, sizeof(mine), hipMemcpyHostToDevice, s));
-    NCCL_TRY(ncclAllGather(e->g_meta.p, e->g_meta.p + 2, 2, ncclInt64, c->comm, s));
-    out.assign(2 * (size_t)W, 0);
-    HIP_TRY(hipMemcpyAsync(out.data(), e->g_meta.p + 2, out.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return AID_OK;
-}
-
-int aid_index_allgather(aid_engine *e, aid_comm *c, int64_t first, int64_t *n_total) {
-    if (!e || !c || !c->comm) return fail(AID_ERR_INVALID, "aid_index_allgather: null argument");
-    if (c->device != e->device) return fail(AID_ERR_INVALID, "aid_index_allgather: comm and engine on different devices");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->own_stream;
-    if (int rc = settle_postings(e)) return rc;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    const int W = c->world;
-    // aid_comm_create reserved this engine's meta buffer; a comm made with another engine gets it here (16 B per
-    // rank: returning early instead would leave the other ranks blocked in the first all-gather)
-    HIP_TRY(e->g_meta.reserve(2 * (size_t)W + 2));
-    // Every rank runs the same collectives whatever happens locally: (1) (count, n_tracks), (2) one ok flag
-    // per rank after every step that can fail locally, (3) the payload only when every rank is ready. A
-    // rank-local failure (bad arguments, OOM of the exchange buffers or the grown index, the pack) is
-    // therefore seen by all ranks before the payload all-gather, and every rank returns an error with its
-    // index unchanged instead of leaving its peers blocked in RCCL.
-    int64_t n_local = -1;
-    uint32_t nt = 0;
-    const int bad = shard_info_locked(e, first, &n_local, &nt);
-    std::vector<int64_t> meta;
-    if (int rc = allgather_pair(e, c, bad ? -1 : n_local, (int64_t)nt, meta, s)) return rc;
-    int64_t mx = 0, tot = 0;
-    uint32_t tracks = 0;
-    std::vector<int64_t> counts(W);
-    for (int r = 0; r < W; ++r) {
-        if (meta[2 * r] < 0) return bad ? bad : fail(AID_ERR_INVALID, "aid_index_allgather: another rank's shard is invalid");
-        counts[r] = meta[2 * r];
-        mx = std::max(mx, counts[r]);
-        tot += counts[r];
-        tracks = std::max(tracks, (uint32_t)meta[2 * r + 1]);
-    }
-    // 2. local preparation: the exchange buffers ([3][mx] own planes, [W][3][mx] received; scratch of this
-    //    call only: ~(W + 1) x 12 B per largest-shard posting), the grown index, the pack of the own shard
-    int rc = AID_OK;
-    if (mx > 0) {
-        hipError_t he = e->g_send.reserve(3 * (size_t)mx);
-        if (he == hipSuccess) he = e->g_recv.reserve(3 * (size_t)mx * W);
-        if (he != hipSuccess)
-            rc = fail(he == hipErrorOutOfMemory ? AID_ERR_NOMEM : AID_ERR_DEVICE,
-                      std::string("index exchange buffers: ") + hipGetErrorString(he));
-        if (!rc) rc = splice_reserve_locked(e, first, tot, tracks, s);
-        if (!rc) rc = pack_locked(e, first, e->g_send.p, mx, s);
-        if (!rc) {
-            he = hipStreamSynchronize(s);
-            if (he != hipSuccess) rc = fail(AID_ERR_DEVICE, std::string("index exchange pack: ") + hipGetErrorString(he));
-        }
-    } else {
-        rc = splice_reserve_locked(e, first, 0, tracks, s);
-    }
-    const std::string local_err = rc ? g_err : std::string();
-    std::vector<int64_t> ok;
-    if (int rc2 = allgather_pair(e, c, rc ? 0 : 1, (int64_t)rc, ok, s)) {
-        e->g_send.release();
-        e->g_recv.release();
-        return rc2;
-    }
-    int failed = -1;
-    for (int r = 0; r < W && failed < 0; ++r)
-        if (!ok[2 * r]) failed = r;
-    if (failed >= 0) {
-        e->g_send.release();
-        e->g_recv.release();
-        if (rc) return fail(rc, local_err);
-        return fail(AID_ERR_STATE, "index exchange aborted: rank " + std::to_string(failed) +
-                                       " failed to prepare (error " + std::to_string(ok[2 * failed + 1]) +
-                                       "); this rank's index is unchanged");
-    }
-    if (mx > 0) {
-        // 3. one all-gather of the padded planes, then the union in rank order replaces this rank's shard
-        NCCL_TRY(ncclAllGather(e->g_send.p, e->g_recv.p, 3 * (size_t)mx, ncclUint32, c->comm, s));
-        rc = splice_locked(e, first, e->g_recv.p, W, mx, counts.data(), tracks, s);
-        e->g_send.release();
-        e->g_recv.release();
-        if (rc) return rc;
-    } else if (int rc3 = ensure_tracks(e, tracks, s)) {
-        return rc3;
-    }
-    if (n_total) *n_total = e->n_post;
-    return AID_OK;
-}
-
-int aid_index_export(aid_engine *e, uint32_t *hash, uint32_t *track, uint32_t *t, int64_t first, int64_t count,
-                     int32_t location) {
-    if (!e || first < 0 || count < 0) return fail(AID_ERR_INVALID, "aid_index_export: bad range");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    if (first + count > e->n_post) return fail(AID_ERR_INVALID, "aid_index_export: bad range");
-    if (count == 0) return AID_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    // the posting append of aid_index_add_extracted runs asynchronously on the caller's stream
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    const hipMemcpyKind k = location == AID_PCM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIP_TRY(hipMemcpy(hash, e->p_hash.p + first, count * sizeof(uint32_t), k));
-    HIP_TRY(hipMemcpy(track, e->p_track.p + first, count * sizeof(uint32_t), k));
-    HIP_TRY(hipMemcpy(t, e->p_t.p + first, count * sizeof(uint32_t), k));
-    return AID_OK;
-}
-
-int aid_index_checksum(aid_engine *e, int64_t first, int64_t count, uint64_t *out) {
-    if (!e || !out || first < 0 || count < 0) return fail(AID_ERR_INVALID, "aid_index_checksum: bad range");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (int rc = settle_postings(e)) return rc;
-    if (first + count > e->n_post) return fail(AID_ERR_INVALID, "aid_index_checksum: bad range");
-    HIP_TRY(hipSetDevice(e->device));
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    HIP_TRY(e->chk.reserve(1));
-    hipStream_t s = e->own_stream;
-    HIP_TRY(hipMemsetAsync(e->chk.p, 0, sizeof(unsigned long long), s));
-    launch_index_checksum(e->p_hash.p, e->p_track.p, e->p_t.p, first, count, e->chk.p, s);
-    HIP_TRY(hipGetLastError());
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, e->chk.p, sizeof(v), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *out = (uint64_t)v;
-    return AID_OK;
-}
-
-int aid_index_csr_export(aid_engine *e, uint32_t *offsets, int64_t n_offsets, uint64_t *posts, int64_t cap,
-                         int64_t *n_out) {
-    if (!e || !n_out || n_offsets < 0 || cap < 0 || (!offsets && n_offsets > 0) || (!posts && cap > 0))
-        return fail(AID_ERR_INVALID, "aid_index_csr_export: bad argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->index_built || e->index_dirty) return fail(AID_ERR_STATE, "aid_index_csr_export: the index is not finalized");
-    HIP_TRY(hipSetDevice(e->device));
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    const int64_t K = (int64_t)index_keys() + 1;
-    *n_out = e->n_indexed;
-    if (offsets && n_offsets > 0) {
-        if (n_offsets < K) return fail(AID_ERR_INVALID, "aid_index_csr_export: offsets need 2^26 + 1 entries");
-        HIP_TRY(hipMemcpy(offsets, e->idx_off.p, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    if (posts && cap > 0) {
-        const int64_t n = std::min<int64_t>(cap, e->n_indexed);
-        if (n > 0) HIP_TRY(hipMemcpy(posts, e->idx_post.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return AID_OK;
-}
-
-static const char kIdxMagic[8] = {'A', 'I', 'D', 'F', 'P', 'I', 'X', '1'};
-
-int aid_index_save(aid_engine *e, const char *path) {
-    if (!e || !path) return fail(AID_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = settle_postings(e)) return rc;
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return fail(AID_ERR_INVALID, std::string("cannot open ") + path);
-    int64_t hdr[6] = {AID_ABI_VERSION, e->cfg.sample_rate, e->cfg.hop, e->n_post, (int64_t)e->n_tracks, 0};
-    bool ok = std::fwrite(kIdxMagic, 1, 8, f) == 8 && std::fwrite(hdr, sizeof(hdr), 1, f) == 1;
-    std::vector<uint32_t> buf((size_t)std::min<int64_t>(e->n_post, 1 << 24));
-    DevBuf<uint32_t> *cols[3] = {&e->p_hash, &e->p_track, &e->p_t};
-    for (int c = 0; c < 3 && ok; ++c)
-        for (int64_t o = 0; o < e->n_post && ok; o += (int64_t)buf.size()) {
-            const int64_t m = std::min<int64_t>((int64_t)buf.size(), e->n_post - o);
-            if (hipMemcpy(buf.data(), cols[c]->p + o, m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-            else ok = std::fwrite(buf.data(), sizeof(uint32_t), m, f) == (size_t)m;
-        }
-    if (ok && e->n_tracks) ok = std::fwrite(e->h_tomb.data(), 1, e->n_tracks, f) == e->n_tracks;
-    ok = (std::fclose(f) == 0) && ok;
-    if (!ok) return fail(AID_ERR_DEVICE, std::string("failed writing ") + path);
-    return AID_OK;
-}
-
-int aid_index_load(aid_engine *e, const char *path) {
-    if (!e || !path) return fail(AID_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = settle_postings(e)) return rc;
-    // Everything is validated and read into scratch buffers first; the engine's index changes only
-    // once the whole file has been read (a failed load leaves the previous index untouched).
-    struct File {
-        FILE *f;
-        ~File() {
-            if (f) std::fclose(f);
-        }
-    } file{std::fopen(path, "rb")};
-    FILE *f = file.f;
-    if (!f) return fail(AID_ERR_INVALID, std::string("cannot open ") + path);
-    char magic[8];
-    int64_t hdr[6];
-    if (std::fread(magic, 1, 8, f) != 8 || std::memcmp(magic, kIdxMagic, 8) != 0 || std::fread(hdr, sizeof(hdr), 1, f) != 1)
-        return fail(AID_ERR_INVALID, "not an aidfp index file");
-    if (hdr[0] != AID_ABI_VERSION) return fail(AID_ERR_INVALID, "index file written by another ABI version");
-    if (hdr[1] != e->cfg.sample_rate || hdr[2] != e->cfg.hop)
-        return fail(AID_ERR_INVALID, "index sample_rate/hop differ from the engine's");
-    const int64_t n = hdr[3];
-    if (n < 0 || n > 0xFFFFFFFFll || hdr[4] < 0 || hdr[4] > 0xFFFFFFFFll || hdr[5] != 0)
-        return fail(AID_ERR_INVALID, "corrupt index header");
-    const uint32_t nt = (uint32_t)hdr[4];
-    if (std::fseek(f, 0, SEEK_END) != 0) return fail(AID_ERR_INVALID, "cannot size index file");
-    const long long fsize = (long long)ftello(f);
-    const long long want = 8 + (long long)sizeof(hdr) + 12ll * n + (long long)nt;
-    if (fsize != want) return fail(AID_ERR_INVALID, fsize < want ? "truncated index file" : "index file has trailing bytes");
-    if (std::fseek(f, 8 + (long)sizeof(hdr), SEEK_SET) != 0) return fail(AID_ERR_INVALID, "cannot read index file");
-    HIP_TRY(hipSetDevice(e->device));
-    if (e->last_stream) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    DevBuf<uint32_t> cols[3];
-    std::vector<uint32_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(n, 1), 1 << 24));
-    for (int c = 0; c < 3; ++c) {
-        HIP_TRY(cols[c].reserve((size_t)std::max<int64_t>(n, 1)));
-        for (int64_t o = 0; o < n; o += (int64_t)buf.size()) {
-            const int64_t m = std::min<int64_t>((int64_t)buf.size(), n - o);
-            if (std::fread(buf.data(), sizeof(uint32_t), m, f) != (size_t)m) return fail(AID_ERR_INVALID, "truncated index file");
-            HIP_TRY(hipMemcpy(cols[c].p + o, buf.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
-    std::vector<uint8_t> tomb(nt);
-    if (nt && std::fread(tomb.data(), 1, nt, f) != nt) return fail(AID_ERR_INVALID, "truncated index file");
-    DevBuf<uint8_t> dtomb;
-    HIP_TRY(dtomb.reserve(std::max<size_t>(nt, 1024)));
-    if (nt) HIP_TRY(hipMemcpy(dtomb.p, tomb.data(), nt, hipMemcpyHostToDevice));
-    // commit: swap the new planes in (the old ones are released with the scratch)
-    std::swap(e->tomb, dtomb);
-    std::swap(e->p_hash, cols[0]);
-    std::swap(e->p_track, cols[1]);
-    std::swap(e->p_t, cols[2]);
-    e->h_tomb = std::move(tomb);
-    e->n_tracks = nt;
-    e->n_post = n;
-    e->tomb_since_build = 0;
-    e->index_dirty = true;
-    e->index_built = false;
     return AID_OK;
 }
 

@@ -1,6 +1,9 @@
 // engine_internal.h -- what the host files of libaidfp.so share: the engine's state (struct aid_engine), its buffer
-// and profiling helpers, and the few functions engine.cpp (engine, extraction, index, comm) and query.cpp (K5, the
-// query entry points, the exact lane) call across the file boundary. Nothing here is part of the C ABI.
+// and profiling helpers, the prologue of its entry points (EngineCall), and the few functions the host files call
+// across their boundaries. engine.cpp: the engine itself, extraction, resampling, dedup, the vector lane's wrappers,
+// profiling. index_host.cpp: the hash index (aidfp_index.h). index_exchange.cpp: aid_comm and the index exchange
+// (the only file that includes RCCL). query.cpp: K5, the query entry points, the exact lane. Nothing here is part
+// of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +17,7 @@
 #include "../../include/aidfp.h"
 #include "aidfp_buffers.h"
 #include "aidfp_device.h"
+#include "aidfp_index.h"
 #include "aidfp_launch.h"
 #include "aidfp_layout.h"
 #include "aidfp_vector.h"
@@ -23,6 +27,7 @@
 using namespace aid;
 
 int fail(int code, const std::string &msg);  // engine.cpp: keeps msg for aid_last_error, returns code
+const std::string &last_error_text();        // engine.cpp: the calling thread's last fail() message
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -102,33 +107,7 @@ struct aid_engine {
     HostBuf<uint8_t> h_synth;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
     Event synth_ev;
 
-    // index (FPSPEC 7): all postings (SoA source of truth) + the CSR built from them
-    DevBuf<uint32_t> p_hash, p_track, p_t;
-    int64_t n_post = 0;  // exact unless post_pend: then the last aid_index_add_extracted's count is in flight
-    // aid_index_add_extracted appends without waiting for its clips' counts: K_append scans them on the device and
-    // the new total comes back to pinned h_npost behind add_ev; settle_postings() makes n_post exact again
-    DevBuf<int64_t> d_npost;
-    HostBuf<int64_t> h_npost;
-    Event add_ev;  // after the last append's staging copies (and, if post_pend, its count copy)
-    bool post_pend = false;
-    std::vector<uint8_t> h_tomb;  // per track id: 1 = removed
-    DevBuf<uint8_t> tomb;
-    uint32_t n_tracks = 0;        // max track id + 1
-    DevBuf<uint32_t> idx_cnt, idx_off, scan_tmp;
-    DevBuf<uint64_t> idx_post;
-    DevBuf<uint16_t> idx_sig;  // K5's 2-B vote signature per CSR posting (aidfp_layout.h posting_sig)
-    DevBuf<uint32_t> srt_k0, srt_k1;  // K4 sort build: key double buffer
-    DevBuf<uint64_t> srt_v;           // K4 sort build: the value buffer idx_post pairs with
-    DevBuf<uint8_t> srt_tmp;          // K4 rocPRIM build (A/B): its temporary storage
-    DevBuf<uint32_t> srt_scratch;     // K4 radix build: per-tile digit counts, their scan, scan temporary
-    int k4_mode = 2;                  // internal K4 build: 2 radix sort (the default; K4_BUILD force 0, 1 or 4),
-                                      // 1 rocPRIM sort (force 3, variant build only), 0 atomic counting sort (force 2)
-    int k4_rank = 0;                  // radix sort's in-wave rank: 0 one LDS atomic per posting where the device
-                                      // serves same-address lanes in order (else ballots), 1 ballots (K4_BUILD 4)
-    bool index_built = false, index_dirty = true;
-    int64_t n_indexed = 0;
-    DevBuf<unsigned long long> nz;
-    DevBuf<unsigned long long> chk;  // aid_index_checksum result
+    HashIndex idx;  // hash index (FPSPEC 7): postings, track table, CSR, K4 and exchange scratch (aidfp_index.h)
     // query workspaces
     DevBuf<uint64_t> q_recs;
     DevBuf<int64_t> q_start, q_count;
@@ -142,13 +121,13 @@ struct aid_engine {
     // collected tickets, reused: their buffers and event stay allocated
     std::vector<std::unique_ptr<aid_query_ticket>> ticket_pool;
     DevBuf<int64_t> q_votes;  // exact votes per query (LDS-histogram eligibility)
-    DevBuf<int64_t> x_src, x_dst;
+    DevBuf<int64_t> q_gsc;    // K5 global pass: record starts and counts of the queries it runs ([0, n), [n, 2n))
+    DevBuf<int32_t> q_grows;  // K5 global pass: their rows [n][max_results][5], then their n row counts
     // batched exact lane (aid_exact_lane): PCM staging, window descriptors, consensus output
     DevBuf<float> x_in, x_win;
     DevBuf<int64_t> x_wdesc;
     DevBuf<int32_t> x_order, x_clipwin, x_nout;
     DevBuf<double> x_out;  // aid_exact_row, 3 x 8 bytes each
-    DevBuf<int64_t> g_meta;            // all-gather: (count, n_tracks) per rank
     std::map<std::pair<int32_t, int32_t>, DevBuf<float>> rs_taps;  // (up, down) -> device [up][J] taps
     // Chromaprint dedup catalog (insertion order) + scan scratch
     DevBuf<uint32_t> dd_words;
@@ -159,11 +138,8 @@ struct aid_engine {
     DevBuf<int64_t> dq_off, dq_off2, dq_idx, dq_pidx;
     DevBuf<double> dq_lo, dq_hi, dq_sim, dq_psim;
     VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
-    DevBuf<uint32_t> g_send, g_recv;   // all-gather: [3][max] SoA planes per rank
-    DevBuf<uint32_t> x_tracks;
     size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
 
-    HostBuf<int64_t> h_stage;  // pinned staging of aid_index_add_extracted
     HostBuf<ClipDesc> h_desc;  // pinned
     // extraction call hazards, tracked with events instead of a stream sync per call:
     // h_desc is the source of an async H2D copy; pcm_stage is read by K1
@@ -183,12 +159,10 @@ struct aid_engine {
     int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
     int lane_gather = 0;           // aid_engine_force LANE_GATHER: stage the exact lane's sub-windows (A/B)
     int64_t plane_rows = 0;        // aid_engine_force PLANE_ROWS: power rows per K1 -> K2 clip group (0 = kPlaneRows)
-    int inject_exchange_fail = 0;  // aid_engine_force EXCHANGE_FAIL: the next exchange's prepare step fails (tests)
     // aid_match_stats: queries, exact votes, and the postings K5 read (a vote = one 8-B posting per pass)
     int64_t st_queries = 0, st_votes = 0, st_post_reads = 0, st_q_global = 0, st_q_lds = 0, st_records = 0;
     int64_t st_sig_reads = 0;  // 2-B posting signatures the LDS path read (two per vote: counting and insert passes)
     int64_t st_fb_reason[5] = {0, 0, 0, 0, 0};  // LDS-path fallbacks (speculative pass) by reason (index.hip)
-    int64_t tomb_since_build = 0;  // removals after the last CSR build (queries must check tomb[])
     size_t k5_batch = 2048;        // global-path queries per launch
     hipStream_t last_stream = nullptr;
     bool have_result = false;
@@ -295,11 +269,45 @@ static inline int check_clips(const char *fn, aid_engine *e, const void *pcm, co
     return AID_OK;
 }
 
-// engine lock held, both; defined among engine.cpp's extern "C" functions, hence the linkage
-extern "C" {
-int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                   void *stream, const int64_t *ends = nullptr);
-int ensure_index(aid_engine *e);  // (re)builds the CSR if postings changed since the last build
-}  // extern "C"
+// The prologue of an entry point that works on the engine's state: null check, the engine lock (held while the
+// object lives), the engine's device made current, then on request the in-flight append settled and one wait for
+// the stream of the last extraction. `s` is the call's stream. Usage: EngineCall call(e, ...); if (call.rc) return
+// call.rc;
+enum LastWait {
+    kNoWait,     // none: the call reads host state only, or queues behind last_stream itself
+    kDrainLast,  // last_stream drained: the call reads what the last extraction or append wrote
+    kOrderLast,  // last_stream drained only if it is not the call's own stream
+};
+struct EngineCall {
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    int rc = AID_OK;
+    EngineCall(aid_engine *e, void *stream = nullptr, bool settle = false, LastWait w = kNoWait) {
+        if (!e) {
+            rc = fail(AID_ERR_INVALID, "null engine");
+            return;
+        }
+        lk = std::unique_lock<std::mutex>(e->mu);
+        s = pick_stream(e, stream);
+        rc = enter(e, s, settle, w);
+    }
+    // the same steps for code that already holds the lock (ensure_index's build)
+    static int enter(aid_engine *e, hipStream_t s, bool settle, LastWait w) {
+        HIP_TRY(hipSetDevice(e->device));
+        if (settle)
+            if (int r = settle_postings(e)) return r;
+        return wait_last(e, s, w);
+    }
+    // the wait alone, for a call whose argument checks against engine state come before it
+    static int wait_last(aid_engine *e, hipStream_t s, LastWait w) {
+        if (w != kNoWait && e->last_stream && !(w == kOrderLast && e->last_stream == s))
+            HIP_TRY(hipStreamSynchronize(e->last_stream));
+        return AID_OK;
+    }
+};
+
+// engine lock held; defined among engine.cpp's extern "C" functions, hence the linkage
+extern "C" int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                              int32_t loc, void *stream, const int64_t *ends = nullptr);
 
 #pragma GCC visibility pop

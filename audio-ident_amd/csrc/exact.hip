@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64) void k_exact_consensus(const int32_t *__restric
     if (lane == 0) n_out[c] = min(kept, max_out);
 }
 
-// Rows of a K5 batch written to scratch (x_dst) land at their query's slot of the device row
+// Rows of a K5 batch written to scratch (q_grows) land at their query's slot of the device row
 // table, so the consensus reads every query's rows from one place.
 __global__ __launch_bounds__(256) void k_rows_scatter(const int32_t *__restrict__ src, const int32_t *__restrict__ order,
                                                       int n, int mr, int32_t *__restrict__ dst) {

@@ -113,8 +113,8 @@ __global__ __launch_bounds__(1024) void k_scan_add(uint32_t *__restrict__ out, c
     if (i < n) out[i] += boff[blockIdx.x];
 }
 
-// K5's 2-B vote signatures of the CSR's postings (aidfp_layout.h posting_sig), for the builds that do not write
-// them in their last pass (the atomic build and the rocPRIM A/B; the radix build fuses it)
+// K5's 2-B vote signatures of the CSR's postings (aidfp_layout.h posting_sig), for the build that does not write
+// them in its last pass (the atomic build; the radix build fuses it)
 __global__ __launch_bounds__(256) void k_make_sig(const uint64_t *__restrict__ post, int64_t n, uint16_t *__restrict__ sig) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t v = post[i];

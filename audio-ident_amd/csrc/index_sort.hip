@@ -1,6 +1,4 @@
-// index_sort.hip -- K4 index build as a key sort: a hand-written LSD radix sort for gfx950 (default),
-// rocPRIM's onesweep kept only as an A/B reference (aid_engine_force K4_BUILD 3), compiled only into the
-// diagnostic variant build -DAID_K4_ROCPRIM_AB (build_ext.build(variant="k4rocprim")), never into libaidfp.so.
+// index_sort.hip -- K4 index build as a key sort: a hand-written LSD radix sort for gfx950.
 //
 // Replaces the LMDB put of `olaf_c store` (audio-ident-service/app/audio/fingerprint.py:117-125;
 // SURVEY.md 8a row a4). The index is a direct-address CSR over key26 = bucket_key(hash) (aidfp_layout.h, a bit
@@ -35,10 +33,6 @@
 // Bytes per posting: 4 (count 1) + 24 (scatter 1) + 2 x 4 (counts 2, 3) + 24 (scatter 2) + 20 (scatter 3) = 80,
 // plus ~4 per distinct key (E) and the 2 KB of counts per tile per pass.
 #include <atomic>
-
-#ifdef AID_K4_ROCPRIM_AB  // diagnostic variant build only (build_ext.build(variant="k4rocprim")); never in libaidfp.so
-#include <rocprim/device/device_radix_sort.hpp>
-#endif
 
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
@@ -389,25 +383,6 @@ __global__ __launch_bounds__(kSortThreads, 3) void k_radix_scatter(const uint32_
     }
 }
 
-// E[key + 1] = i + 1 at the last posting i of each live key's run (E zeroed by the caller); nz += number of
-// live keys (one atomic per workgroup)
-__global__ __launch_bounds__(256) void k_run_ends(const uint32_t *__restrict__ keys, int64_t n,
-                                                  uint32_t *__restrict__ E, unsigned long long *__restrict__ nz) {
-    __shared__ unsigned long long part[4];
-    unsigned long long c = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t k = keys[i];
-        if (k < (1u << 26) && (i == n - 1 || keys[i + 1] != k)) {
-            E[k + 1] = (uint32_t)(i + 1);
-            ++c;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(nz, part[0] + part[1] + part[2] + part[3]);
-}
-
 // ---- scans over u32 (8 items per thread, wave shuffles): exclusive sum (tile counts) and inclusive max
 // (offsets from run ends). Level 1 per 8192-item block; the block totals are scanned recursively and folded
 // back into every block.
@@ -567,19 +542,6 @@ static int lds_lane_order_ok(uint32_t *dev_word, hipStream_t s) {
     return viol == 0 ? 1 : 0;
 }
 
-// ---- rocPRIM reference build (A/B only, in the AID_K4_ROCPRIM_AB variant build) ----
-#ifdef AID_K4_ROCPRIM_AB
-__global__ void k_sort_keys(const uint32_t *__restrict__ ph, const uint32_t *__restrict__ ptrack,
-                            const uint32_t *__restrict__ pt, int64_t n, const uint8_t *__restrict__ tomb,
-                            uint32_t n_tracks, uint32_t *__restrict__ keys, uint64_t *__restrict__ vals) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t tr = ptrack[i];
-        keys[i] = make_key(ph[i], tr, tomb, n_tracks);
-        vals[i] = (uint64_t)tr | ((uint64_t)pt[i] << 32);
-    }
-}
-#endif
-
 int64_t radix_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
 
 // scratch of the sort build in u32 units: the tile counts, their scan, and the scans' temporaries
@@ -588,28 +550,6 @@ size_t radix_scratch_u32(int64_t n) {
     return (size_t)(2 * c) +
            std::max<size_t>(2 * (size_t)kDigits * (col_groups(radix_tiles(n)) + 1), scan8_tmp((int64_t)(1u << 26) + 1)) +
            64;
-}
-
-// temporary storage of the rocPRIM sort for n pairs
-size_t index_sort_temp_bytes(int64_t n) {
-#ifdef AID_K4_ROCPRIM_AB
-    size_t bytes = 0;
-    rocprim::double_buffer<uint32_t> k(nullptr, nullptr);
-    rocprim::double_buffer<uint64_t> v(nullptr, nullptr);
-    if (rocprim::radix_sort_pairs(nullptr, bytes, k, v, (size_t)n, 0, kSortKeyBits) != hipSuccess) return 0;
-    return bytes;
-#else
-    (void)n;
-    return 0;
-#endif
-}
-
-bool k4_ab_sort_built() {
-#ifdef AID_K4_ROCPRIM_AB
-    return true;
-#else
-    return false;
-#endif
 }
 
 // the three passes of the hand-written sort: SoA postings -> (keys1, vals1) -> (keys0, vals0) -> the CSR's values in
@@ -653,35 +593,18 @@ static void radix_passes(const uint32_t *ph, const uint32_t *ptrack, const uint3
 
 // keys0/keys1: n u32 each; vals0/vals1: n u64 each (the sorted values end in *vals_out, one of the two).
 // E (2^26 + 1 u32, zeroed by the caller) receives the run ends, offsets the CSR offsets, *nz (zeroed) the
-// number of live keys. use_rocprim: the A/B reference (temp/temp_bytes its storage); `scratch` holds
-// radix_scratch_u32(n) u32 either way (the offsets scan uses it too).
+// number of live keys. `scratch` holds radix_scratch_u32(n) u32 (the offsets scan uses it too).
 hipError_t launch_index_sort_build(const uint32_t *ph, const uint32_t *ptrack, const uint32_t *pt, int64_t n,
                                    const uint8_t *tomb, uint32_t n_tracks, uint32_t *keys0, uint32_t *keys1,
-                                   uint64_t *vals0, uint64_t *vals1, void *temp, size_t temp_bytes, bool use_rocprim,
-                                   uint32_t *scratch, uint32_t *E, uint32_t *offsets, unsigned long long *nz,
-                                   uint64_t **vals_out, uint16_t *sig, int rank_mode, hipStream_t s) {
+                                   uint64_t *vals0, uint64_t *vals1, uint32_t *scratch, uint32_t *E, uint32_t *offsets,
+                                   unsigned long long *nz, uint64_t **vals_out, uint16_t *sig, int rank_mode,
+                                   hipStream_t s) {
     *vals_out = vals0;
     const int64_t K = (int64_t)(1u << 26) + 1;
     const int64_t tiles = radix_tiles(n);
     const int64_t c = (int64_t)kDigits * tiles;
     uint32_t *stmp = scratch + 2 * c;
-    const uint32_t *sorted_keys = nullptr;
-    if (n > 0 && use_rocprim) {
-#ifndef AID_K4_ROCPRIM_AB
-        return hipErrorNotSupported;
-#else
-        const int64_t blocks = std::min<int64_t>((n + 255) / 256, 16384);
-        hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)blocks), dim3(256), 0, s, ph, ptrack, pt, n, tomb, n_tracks,
-                           keys0, vals0);
-        rocprim::double_buffer<uint32_t> k(keys0, keys1);
-        rocprim::double_buffer<uint64_t> v(vals0, vals1);
-        size_t bytes = temp_bytes;
-        hipError_t err = rocprim::radix_sort_pairs(temp, bytes, k, v, (size_t)n, 0, kSortKeyBits, s);
-        if (err != hipSuccess) return err;
-        sorted_keys = k.current();
-        *vals_out = v.current();
-#endif
-    } else if (n > 0) {
+    if (n > 0) {
         uint32_t *counts = scratch, *offs = scratch + c;
         // rank_mode 0: the one-atomic rank where the device serves same-address LDS lanes in order, 1: ballots
         bool arank = false;
@@ -698,15 +621,8 @@ hipError_t launch_index_sort_build(const uint32_t *ph, const uint32_t *ptrack, c
                                 tiles, s);
         *vals_out = vals1;
     }
-#ifdef AID_K4_ROCPRIM_AB
-    if (n > 0 && sorted_keys) {  // rocPRIM: run ends from its sorted keys, the signatures from its values
-        const int64_t blocks = std::min<int64_t>((n + 255) / 256, 16384);
-        hipLaunchKernelGGL(k_run_ends, dim3((unsigned)blocks), dim3(256), 0, s, sorted_keys, n, E, nz);
-        launch_make_sig(*vals_out, n, sig, s);
-    }
-#endif
-    // the hand-written sort wrote E in its last pass; its live keys are the nonzero E entries
-    scan8<true>(E, offsets, K, stmp, s, sorted_keys ? nullptr : nz);
+    // the sort wrote E in its last pass; its live keys are the nonzero E entries
+    scan8<true>(E, offsets, K, stmp, s, nz);
     return hipGetLastError();
 }
 

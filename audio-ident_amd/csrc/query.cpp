@@ -1,6 +1,6 @@
 // query.cpp -- the query half of libaidfp.so's host side: K5's orchestration, the query entry points (synchronous,
-// and the submit / collect pair with its tickets) and the batched exact lane. Extraction and the index live in
-// engine.cpp; engine_internal.h is what the two share.
+// and the submit / collect pair with its tickets) and the batched exact lane. Extraction lives in engine.cpp, the
+// index in index_host.cpp (K5 reads it through HashIndex::view()); engine_internal.h is what the host files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +37,7 @@ constexpr double kForwardedPerBucket = 2.0;  // forwarded votes (1-bit filter es
 static int k5_enqueue(aid_engine *e, const uint64_t *recs, const int64_t *qstart_dev, const int64_t *qcount_dev, int nq,
                       int64_t rec_cap, bool lds, bool want_rows, K5Host &h, hipStream_t s, bool have_starts = false) {
     const int mr = e->cfg.max_results;
+    const CsrView ix = e->idx.view();
     HIP_TRY(e->q_rows.reserve((size_t)std::max(nq, 1) * mr * 5));
     HIP_TRY(e->q_nrows.reserve((size_t)std::max(nq, 1)));
     HIP_TRY(e->q_votes.reserve((size_t)nq));
@@ -47,15 +48,14 @@ static int k5_enqueue(aid_engine *e, const uint64_t *recs, const int64_t *qstart
     int64_t *p_start = h.meta.p, *p_count = p_start + nq, *p_votes = p_count + nq;
     if (!have_starts) HIP_TRY(hipMemcpyAsync(p_start, qstart_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(p_count, qcount_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    launch_query_votes(recs, qstart_dev, qcount_dev, nq, e->idx_off.p, e->q_votes.p, lds ? e->q_ranges.p : nullptr, s);
+    launch_query_votes(recs, qstart_dev, qcount_dev, nq, ix.offsets, e->q_votes.p, lds ? e->q_ranges.p : nullptr, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(p_votes, e->q_votes.p, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     if (!lds) return AID_OK;
     {
         ProfScope ps(e, AID_K_MATCH, s, true);
-        launch_match_lds(recs, qstart_dev, qcount_dev, nq, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                         e->cfg.min_match, mr, e->q_rows.p, e->q_nrows.p, e->tomb_since_build > 0, e->q_votes.p,
-                         e->idx_sig.p, e->q_ranges.p, s);
+        launch_match_lds(recs, qstart_dev, qcount_dev, nq, ix.offsets, ix.post, ix.tomb, ix.n_tracks, e->cfg.min_match,
+                         mr, e->q_rows.p, e->q_nrows.p, ix.check_tomb, e->q_votes.p, ix.sig, e->q_ranges.p, s);
     }
     HIP_TRY(hipGetLastError());
     if (want_rows)
@@ -100,6 +100,7 @@ static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start
                      const int64_t *h_votes, int64_t vmax, std::vector<int> todo, aid_match_row *rows, int32_t *nrows,
                      hipStream_t s) {
     const int mr = e->cfg.max_results;
+    const CsrView ix = e->idx.view();
     const double votes = (double)vmax;
     const int parts = e->k5_parts > 0 ? e->k5_parts : votes > (double)(1 << 18) ? 2 : 1;
     const double m_seen = (double)(1 << 20), vp = votes / parts;
@@ -120,17 +121,16 @@ static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start
         }
         const std::vector<int> &order = todo;
         const int n = (int)order.size();
-        // gather the queries' ranges into x_src; their rows and counts come out in x_dst
-        HIP_TRY(e->x_src.reserve(2 * order.size()));
+        // gather the queries' ranges into q_gsc; their rows and counts come out in q_grows
+        HIP_TRY(e->q_gsc.reserve(2 * order.size()));
         std::vector<int64_t> st(order.size()), ct(order.size());
         for (size_t i = 0; i < order.size(); ++i) { st[i] = h_start[order[i]]; ct[i] = h_count[order[i]]; }
-        HIP_TRY(hipMemcpyAsync(e->x_src.p, st.data(), st.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(e->x_src.p + order.size(), ct.data(), ct.size() * sizeof(int64_t),
+        HIP_TRY(hipMemcpyAsync(e->q_gsc.p, st.data(), st.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(e->q_gsc.p + order.size(), ct.data(), ct.size() * sizeof(int64_t),
                                hipMemcpyHostToDevice, s));
-        const int64_t *qs = e->x_src.p, *qc = e->x_src.p + order.size();
-        HIP_TRY(e->x_dst.reserve(((size_t)order.size() * mr * 5 + 1) / 2 + order.size()));
-        int32_t *out_rows = reinterpret_cast<int32_t *>(e->x_dst.p);
-        int32_t *out_n = out_rows + (size_t)order.size() * mr * 5;
+        const int64_t *qs = e->q_gsc.p, *qc = e->q_gsc.p + order.size();
+        HIP_TRY(e->q_grows.reserve(order.size() * ((size_t)mr * 5 + 1)));
+        int32_t *out_rows = e->q_grows.p, *out_n = out_rows + (size_t)order.size() * mr * 5;
         // from the second global attempt on, the distinct (slot, t_q) sets live in HBM (2^dbits entries per query,
         // 4x more per attempt): a query that overflowed k_vote_final's LDS set is a long one with a strong match
         // (FPSPEC v1 7), which more histogram buckets do not help
@@ -146,10 +146,9 @@ static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start
             // K5a, K5h, K5b, each with its own dispatch-attached events when profiled
             for (int stage = 1; stage <= 3; ++stage) {
                 ProfScope ps(e, stage == 1 ? AID_K_VOTE_HIST : stage == 2 ? AID_K_HOT_SCAN : AID_K_VOTE_FINAL, s, true);
-                launch_query(recs, qs + q0, qc + q0, nb, e->idx_off.p, e->idx_post.p, e->tomb.p, e->n_tracks,
-                             e->cfg.min_match, mr, e->q_hist.p, bits, e->q_hot.p, out_rows + (size_t)q0 * mr * 5,
-                             out_n + q0, e->tomb_since_build > 0, parts, stage, dbits ? e->q_dset.p : nullptr, dbits,
-                             s);
+                launch_query(recs, qs + q0, qc + q0, nb, ix.offsets, ix.post, ix.tomb, ix.n_tracks, e->cfg.min_match,
+                             mr, e->q_hist.p, bits, e->q_hot.p, out_rows + (size_t)q0 * mr * 5, out_n + q0,
+                             ix.check_tomb, parts, stage, dbits ? e->q_dset.p : nullptr, dbits, s);
             }
             HIP_TRY(hipGetLastError());
         }

@@ -103,8 +103,8 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
 #define AID_FORCE_K5_PARTS 2       /* 0 by vote count, else 1, 2 or 4 key partitions per query (K5a) */
 #define AID_FORCE_K5_BATCH 3       /* 0 default (2048), else global-path queries per launch */
 #define AID_FORCE_K2_STRIPS_X100 4 /* 0 adaptive, else 100 x K2 strips per resident workgroup slot */
-#define AID_FORCE_K4_BUILD 5       /* 0 default, 1 radix sort (the default), 2 atomic counting sort, 3 rocPRIM sort (A/B; only in the
-                                      diagnostic variant library, else AID_ERR_INVALID),
+#define AID_FORCE_K4_BUILD 5       /* 0 default, 1 radix sort (the default), 2 atomic counting sort (A/B), 3 retired
+                                      (a library sort once kept for A/B: AID_ERR_INVALID),
                                       4 radix sort with the ballot-matched in-wave rank (A/B of the one-atomic rank) */
 #define AID_FORCE_EXCHANGE_FAIL 6  /* 1: the next index exchange's pack (aid_index_pack, or the prepare step of
                                       aid_index_allgather) fails with AID_ERR_NOMEM, once (rank-failure tests) */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K4 index build A/B on the config-3 catalog: hand-written radix sort vs rocPRIM vs the atomic build.
+"""K4 index build A/B on the config-3 catalog: hand-written radix sort vs the atomic build.
 
     python probes/k4_probe.py [--tracks 100000] [--reps 3]
 
@@ -23,8 +23,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tracks", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--modes", default="radix,rocprim,atomic,radix_again",
-                    help="builds to time, of radix, rocprim, atomic, radix_again, radix_ballot (the ballot-matched "
+    ap.add_argument("--modes", default="radix,atomic,radix_again",
+                    help="builds to time, of radix, atomic, radix_again, radix_ballot (the ballot-matched "
                          "in-wave rank) (AIDFP_LIB picks an A/B library)")
     args = ap.parse_args()
     import torch
@@ -39,7 +39,7 @@ def main():
 
     out = {"postings": st.postings_total, "library": os.environ.get("AIDFP_LIB", "product")}
     ref = None
-    modes = [m for m in (("radix", 1), ("rocprim", 3), ("atomic", 2), ("radix_again", 1), ("radix_ballot", 4))
+    modes = [m for m in (("radix", 1), ("atomic", 2), ("radix_again", 1), ("radix_ballot", 4))
              if m[0] in args.modes.split(",")]
     for name, mode in modes:
         eng.force("k4_build", mode)
@@ -63,13 +63,10 @@ def main():
                      "live": stats["live"], "same_live_as_radix": stats["live"] == ref["live"],
                      "bytes_per_posting_at_event_time": None}
     n = st.postings_total
-    for name in ("radix", "rocprim"):
-        if name not in out:
-            continue
-        best = min(out[name]["event_ms"])
-        out[name]["best_event_ms"] = best
-        out[name]["gb_per_s_at_92B" if name == "radix" else "gb_per_s_at_125B"] = round(
-            n * (92 if name == "radix" else 125) / (best * 1e-3) / 1e9, 1)
+    if "radix" in out:
+        best = min(out["radix"]["event_ms"])
+        out["radix"]["best_event_ms"] = best
+        out["radix"]["gb_per_s_at_92B"] = round(n * 92 / (best * 1e-3) / 1e9, 1)
     print(json.dumps(out), flush=True)
     eng.close()
 

@@ -60,8 +60,8 @@ def test_resample_len_without_gpu():
 
 
 def test_product_library_links_no_rocprim():
-    """rocPRIM's radix sort is the K4 A/B reference of the diagnostic variant build only; the product
-    library defines no symbol of it (its code would appear as rocprim:: template instances)."""
+    """rocPRIM's radix sort, once K4's A/B reference, is gone; the library defines no symbol of it
+    (its code would appear as rocprim:: template instances)."""
     import shutil
     import subprocess
 

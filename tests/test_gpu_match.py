@@ -389,8 +389,8 @@ def test_csr_layout_equals_stable_mirror(mode):
 
 
 def test_rocprim_ab_not_in_product_library():
-    """The rocPRIM sort is an A/B reference of the diagnostic variant build only: the product
-    library refuses k4_build 3 and links no rocPRIM code."""
+    """The rocPRIM sort that k4_build 3 once selected for A/B is gone: the library refuses the number
+    and links no rocPRIM code."""
     from aidfp._lib import EngineError
 
     eng = Engine(SR)
@@ -454,7 +454,7 @@ def test_csr_layout_small_and_tile_edges(mode, n):
 
 def test_async_append_equals_per_clip_records(tmp_path):
     """aid_index_add_extracted appends without waiting for its batch's counts (offsets scanned on the device, the
-    new total read back by the next reader; engine.cpp settle_postings): batches of every size, a silent clip and
+    new total read back by the next reader; index_host.cpp settle_postings): batches of every size, a silent clip and
     one shorter than a frame, readers and a host append between them, and batches beyond the planes' headroom
     (the growth path, counts read back first) store exactly each clip's records under its track, in call order."""
     sr = 16000
