@@ -84,6 +84,9 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     if (call.rc) return call.rc;
     if (!track_ids && e->n_clips > 0) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad argument");
     if (!e->have_result) return fail(AID_ERR_STATE, "no extraction to index");
+    // 0xFFFFFFFF is K5's empty-slot marker (and track + 1 would wrap to 0 below), as in aid_index_add_track
+    for (int c = 0; c < e->n_clips; ++c)
+        if (track_ids[c] == 0xFFFFFFFFu) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad track id");
     HashIndex &ix = e->idx;
     hipStream_t s = e->last_stream ? e->last_stream : call.s;  // behind the extraction, without waiting for it
     const int n = e->n_clips;
@@ -158,15 +161,19 @@ int aid_index_add_postings(aid_engine *e, const uint32_t *hash, const uint32_t *
     if (call.rc) return call.rc;
     HashIndex &ix = e->idx;
     hipStream_t s = call.s;
-    uint32_t mx = 0;
+    // the largest track id; 0xFFFFFFFF is K5's empty-slot marker (with d = -1 also the empty (track, d) key), and
+    // id + 1 would wrap to 0: rejected before anything is grown or copied, as in aid_index_add_track
+    uint32_t top = 0;
     if (location == AID_PCM_HOST) {
-        for (int64_t i = 0; i < n; ++i) mx = std::max(mx, track[i] + 1);
+        for (int64_t i = 0; i < n; ++i) top = std::max(top, track[i]);
     } else {
         // device track ids: one max-reduction via a host copy of the track column
         std::vector<uint32_t> tr(n);
         HIP_TRY(hipMemcpy(tr.data(), track, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < n; ++i) mx = std::max(mx, tr[i] + 1);
+        for (int64_t i = 0; i < n; ++i) top = std::max(top, tr[i]);
     }
+    if (top == 0xFFFFFFFFu) return fail(AID_ERR_INVALID, "aid_index_add_postings: bad track id");
+    const uint32_t mx = top + 1;
     if (int rc = grow_postings(e, (size_t)(ix.n_post + n), s)) return rc;
     if (int rc = ensure_tracks(e, mx, s)) return rc;
     const hipMemcpyKind k = location == AID_PCM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;

@@ -212,9 +212,12 @@ typedef struct aid_match_row {
 int aid_index_reset(aid_engine *e);
 /* Add every clip of the last aid_extract as track track_ids[c] (host array of n_clips). Asynchronous: the
    clips' posting counts are scanned on the device and the call does not wait for them (only for the previous
-   call's); every reader of the postings (stats, finalize, export, ...) waits for the count first. */
+   call's); every reader of the postings (stats, finalize, export, ...) waits for the count first.
+   Track id 0xFFFFFFFF is reserved (the matcher's empty-slot marker): AID_ERR_INVALID, nothing is added. */
 int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids);
-/* Add n postings (hash, track, t) from host (AID_PCM_HOST) or device (AID_PCM_DEVICE) arrays. */
+/* Add n postings (hash, track, t) from host (AID_PCM_HOST) or device (AID_PCM_DEVICE) arrays. A posting whose
+   track id is 0xFFFFFFFF (reserved, as for aid_index_add_track) fails the whole call with AID_ERR_INVALID before
+   anything is stored. */
 int aid_index_add_postings(aid_engine *e, const uint32_t *hash, const uint32_t *track, const uint32_t *t, int64_t n,
                            int32_t location);
 /* Register track id `track` without postings (a clip too short or too quiet to give a hash), so a
