@@ -1,4 +1,4 @@
-// aidfp_layout.h -- HBM layout constants shared by host (engine.cpp, query.cpp) and kernels.
+// aidfp_layout.h -- HBM layout constants shared by host (extract.cpp, query.cpp) and kernels.
 #pragma once
 #include <stdint.h>
 

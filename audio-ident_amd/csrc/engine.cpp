@@ -1,11 +1,8 @@
-// engine.cpp -- host side of libaidfp.so: the C ABI of include/aidfp.h.
-//
-// Owns one GPU's tables and workspaces, builds the per-call clip descriptors
-// (one small H2D copy), launches K1..K3 on the caller's stream and exposes the
-// results. Replaces the `olaf_c` process boundary of the reference
-// (audio-ident-service/app/audio/fingerprint.py:87-270). The hash index is index_host.cpp, its exchange between ranks
-// index_exchange.cpp, the query half (K5, the query entry points, the exact lane) query.cpp; engine_internal.h holds
-// what the host files share.
+// engine.cpp -- host side of libaidfp.so, the C ABI of include/aidfp.h, which replaces the `olaf_c` process boundary
+// of the reference (audio-ident-service/app/audio/fingerprint.py:87-270): the engine itself (one GPU's tables and
+// workspaces; create, destroy, force knobs, profiling, stats) and the synth, resample, dedup and vector entry points.
+// Extraction is extract.cpp, the hash index index_host.cpp, its exchange between ranks index_exchange.cpp, the query
+// half (K5, the query entry points, the exact lane) query.cpp; engine_internal.h holds what the host files share.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,7 +21,6 @@ extern "C" int aid_diag_k2_stamps(unsigned long long *out, int reset) {  // diag
 }
 #endif
 
-
 static thread_local std::string g_err;
 
 int fail(int code, const std::string &msg) {
@@ -33,7 +29,6 @@ int fail(int code, const std::string &msg) {
 }
 
 const std::string &last_error_text() { return g_err; }
-
 
 static void build_tables(Tables &t) {
     auto tw = [](int j, int L) {
@@ -103,8 +98,8 @@ int aid_engine_create(const aid_config *cfg, aid_engine **out) {
     std::unique_ptr<aid_engine> e(new aid_engine());  // every early return below frees what was built so far
     e->cfg = c;
     e->device = dev;
-    for (int w = 0; w < 2; ++w) e->k2_slots[w] = (int64_t)prop.multiProcessorCount * peak_pick_blocks_per_cu(2 + 2 * w);
-    e->k1_slots = (int64_t)prop.multiProcessorCount * kStftWaves;
+    for (int w = 0; w < 2; ++w) e->ext.k2_slots[w] = (int64_t)prop.multiProcessorCount * peak_pick_blocks_per_cu(2 + 2 * w);
+    e->ext.k1_slots = (int64_t)prop.multiProcessorCount * kStftWaves;
     // blocking stream: ordered against the legacy default stream (torch's default), so device
     // buffers the caller filled there without a stream handle are complete before NULL-stream calls
     hipError_t he = hipStreamCreateWithFlags(&e->own_stream.s, hipStreamDefault);
@@ -176,12 +171,11 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
             return AID_OK;
         case AID_FORCE_K2_STRIPS_X100:
             if (value < 0) return fail(AID_ERR_INVALID, "K2_STRIPS_X100 must be >= 0");
-            e->k2_slots_x = value / 100.0;
-            e->desc_dev_for_key = nullptr;  // strip bases change: rebuild the descriptors
+            e->ext.k2.force_slots_x = value / 100.0;
             return AID_OK;
         case AID_FORCE_K2_WIDTH:
             if (value != 0 && value != 2 && value != 4) return fail(AID_ERR_INVALID, "K2_WIDTH: 0 adaptive, 2 or 4");
-            e->k2_width_force = value;
+            e->ext.k2.force_width = value;
             return AID_OK;
         case AID_FORCE_K4_BUILD:
             if (value < 0 || value > 4 || value == 3)  // 3 was a library sort kept for A/B; the number stays retired
@@ -200,7 +194,7 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
             return AID_OK;
         case AID_FORCE_PLANE_ROWS:
             if (value < 0) return fail(AID_ERR_INVALID, "PLANE_ROWS must be >= 0");
-            e->plane_rows = value;
+            e->ext.plane_rows = value;
             return AID_OK;
         case AID_FORCE_VEC_PATH:
             if (value < 0 || value > 2) return fail(AID_ERR_INVALID, "VEC_PATH: 0 auto, 1 MFMA, 2 VALU");
@@ -214,396 +208,6 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
         default:
             return fail(AID_ERR_INVALID, "aid_engine_force: unknown path id");
     }
-}
-
-int64_t aid_num_frames(const aid_engine *e, int64_t n) { return e ? num_frames(n, e->cfg.hop) : 0; }
-
-int64_t aid_hash_capacity(const aid_engine *e, int64_t n) { return e ? hash_capacity(num_frames(n, e->cfg.hop)) : 0; }
-
-// power rows per K1 -> K2 clip group of one extraction call (3 GB of plane; extract_locked)
-constexpr int64_t kPlaneRows = (int64_t)3 << 18;
-
-
-static int extract_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets,
-                         int32_t n_clips, int32_t loc, void *stream) {
-    if (int rc = check_clips(fn, e, pcm, offsets, n_clips, loc)) return rc;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return drain_host_copy(e, loc, stream, extract_locked(e, pcm, fmt, offsets, n_clips, loc, stream));
-}
-
-int aid_extract(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc, void *stream) {
-    return extract_entry("aid_extract", e, pcm, kF32, offsets, n_clips, loc, stream);
-}
-
-int aid_extract_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                    void *stream) {
-    return extract_entry("aid_extract_s16", e, pcm, kS16, offsets, n_clips, loc, stream);
-}
-
-// Clip c is pcm[offsets[c], offsets[c + 1]); with `ends` (device PCM only) it is pcm[offsets[c], ends[c]), so
-// clips may overlap (the exact lane's sub-windows are read in place).
-int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
-                   void *stream, const int64_t *ends) {
-    if (ends && loc != AID_PCM_DEVICE) return fail(AID_ERR_INVALID, "extract: clip ends need device PCM");
-    HIP_TRY(hipSetDevice(e->device));
-    auto clip_len = [&](int c) { return (ends ? ends[c] : offsets[c + 1]) - offsets[c]; };
-    hipStream_t s = pick_stream(e, stream);
-    const int hop = e->cfg.hop;
-
-    // descriptors; host PCM is staged as one copy of the clips' span. h_desc is rewritten below, and may be
-    // reallocated here: the previous descriptor upload must have left it
-    HIP_TRY(e->desc_ev.wait());
-    HIP_TRY(e->h_desc.reserve((size_t)n_clips + 1));
-    // a different stream than the previous call's: order against it the simple way
-    if (e->last_stream && e->last_stream != s) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    // same clips, PCM location and strip length as the descriptors already on the device: no re-upload
-    // key: [offset, length] per clip, the PCM location, then the K2 strip length of every clip group and the K2 width
-    // the lengths were sized for (below)
-    bool desc_same = e->desc_dev_for_key == e->desc.p && e->desc.p && e->desc_key.size() > 2 * (size_t)n_clips + 1 &&
-                     e->desc_key[2 * n_clips] == loc;
-    for (int c = 0; desc_same && c < n_clips; ++c)
-        desc_same = e->desc_key[2 * c] == offsets[c] && e->desc_key[2 * c + 1] == clip_len(c);
-    e->clip_base.assign(n_clips, 0);
-    e->clip_frames.assign(n_clips, 0);
-    int64_t frames = 0, strips = 0, chunks = 0, recs = 0, staged = 0, kstrips = 0;
-    bool empty_clip = false;  // a clip without frames gets no count from K3: zero the counts first
-    // K3 (landmarks.hip): a clip of several chunks needs the COUNT pass for its chunk bases; when every clip is
-    // exactly one chunk, a workgroup's clip is its chunk index. Neither follows from the totals alone: a clip
-    // too short for a frame has no chunk, so [short, two-chunk] also has as many chunks as clips
-    bool multi_chunk = false, one_chunk_each = n_clips > 0;
-    for (int c = 0; c < n_clips; ++c) e->clip_frames[c] = num_frames(clip_len(c), hop);
-    // K2 strips per resident workgroup slot. Strip-cold K2 waves exit (peaks.hip) and their
-    // registers admit more workgroups per CU (LDS allows 7 instead of the 4 of an all-hot CU): with the
-    // fraction c of cold waves counted in earlier calls (K3 stores it in pinned memory; read without a sync,
-    // so it lags a few calls), the strips are made shorter and more numerous, 0.75 / (1 - c) per slot,
-    // quantised to 1, 1.25, 1.5 (a stable key for the cached descriptors)
-    //
-    // K2 width (peaks.hip): 2-wave workgroups over bins 0..511 fit 8 to a CU, all of their waves working, where band-
-    // limited audio leaves a CU 4 four-wave workgroups with two cold waves each; but they walk a strip a second time
-    // for bins 512..1023 when its upper half is hot, and K2 ends with its slowest workgroup: with 2 full-band clips
-    // among 256 (0.8 % of the strips walked twice) width 2 already took 0.196 ms against 0.118 at width 4, against
-    // 0.092 / 0.117 with none (profiles/k2_width_ab.txt). So width 2 is for calls in which no strip is walked twice.
-    // K2 counts those strips at width 2, K3 stores the count beside the cold one. From width 4 (the start) the choice
-    // goes to 2 when the cold count of a width-4 call says that there would be none: a strip needs no second walk
-    // exactly when its two upper quarter waves are strip-cold, so none does when half of all waves or more were
-    // cold (cold waves of the lower quarters can overstate this; the count at width 2 then corrects it). From width
-    // 2 it goes back to 4 as soon as a strip was walked twice, and stays there for kK2Hold calls, so a mixed workload
-    // does not flap: one slow call in 64. Counts of a launch at another width than the one in use are not applied
-    // (the words lag a few calls). Results never depend on the width or the strip length. At width 2 nothing exits on
-    // the audio it is chosen for: 1 strip per slot (1.25: K2 0.111 against 0.093 ms).
-    constexpr int kK2Hold = 64;
-    const uint64_t cw = e->h_cold.p ? *reinterpret_cast<volatile uint64_t *>(e->h_cold.p) : 0;
-    const uint64_t sw = e->h_cold.p ? *reinterpret_cast<volatile uint64_t *>(e->h_cold.p + 1) : 0;
-    const int seen_width = (sw >> 32) ? (int)((cw >> 32) / (sw >> 32)) : 0;  // of the launch that was counted
-    int width = e->k2_width_force;
-    if (!width) {
-        if (e->k2_width == 4) {
-            if (e->k2_hold > 0) --e->k2_hold;
-            else if (seen_width == 4 && 2 * (uint64_t)(uint32_t)cw >= (cw >> 32)) e->k2_width = 2;
-        } else if (seen_width == 2 && (uint32_t)sw > 0) {
-            e->k2_width = 4;
-            e->k2_hold = kK2Hold;
-        }
-        width = e->k2_width;
-    } else {
-        e->k2_width = width;
-    }
-    const int64_t k2_slots = e->k2_slots[width == 2 ? 0 : 1];
-    double kx = e->k2_slots_x;
-    if (kx <= 0.0) {
-        kx = 1.0;
-        if (width == 4 && seen_width == 4) {
-            const double c = std::min(1.0, (double)(uint32_t)cw / (double)(cw >> 32));
-            kx = c >= 0.45 ? 1.5 : c >= 0.3 ? 1.25 : 1.0;
-        }
-    }
-    // clip groups: consecutive clips whose frames fit kPlaneRows power rows each run K1 -> K2 on one power buffer.
-    // K1 and K2 run 5-14 % slower per audio-second on a 10.8 GB plane than on a 2.7 GB one
-    // (profiles/r05zo_catalog_batch.txt); a call within the bound (the headline's 256 x 10 s, one catalog batch, a
-    // stream push) is one group, as before. K3 runs once over the whole call's mask. AID_FLAG_KEEP_POWER keeps
-    // every row for aid_result_power: one group.
-    std::vector<int> gstart{0};
-    {
-        const bool keep_all = (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0;
-        const int64_t cap = e->plane_rows > 0 ? e->plane_rows : kPlaneRows;
-        int64_t acc = 0;
-        for (int c = 0; c < n_clips; ++c) {
-            if (!keep_all && acc > 0 && acc + e->clip_frames[c] > cap) {
-                gstart.push_back(c);
-                acc = 0;
-            }
-            acc += e->clip_frames[c];
-        }
-        gstart.push_back(n_clips);
-    }
-    const int n_groups = (int)gstart.size() - 1;
-    std::vector<int> glen(n_groups);
-    std::vector<int64_t> gfirst(n_groups), gframes(n_groups, 0), gstrips(n_groups, 0), gk(n_groups, 0);
-    for (int g = 0; g < n_groups; ++g)  // K2 strips per resident slot, per group (strip_base restarts at 0 in each)
-        glen[g] = peak_strip_len(e->clip_frames.data() + gstart[g], gstart[g + 1] - gstart[g],
-                                 std::max<int64_t>(1, (int64_t)(k2_slots * kx)));
-    // strip bases follow the groups and their strip lengths: (first clip, strip length) per group in the key
-    desc_same = desc_same && e->desc_key.size() == 2 * (size_t)n_clips + 2 + 2 * (size_t)n_groups &&
-                e->desc_key.back() == width;
-    for (int g = 0; desc_same && g < n_groups; ++g)
-        desc_same = e->desc_key[2 * n_clips + 1 + 2 * g] == gstart[g] && e->desc_key[2 * n_clips + 2 + 2 * g] == glen[g];
-    for (int c = 0, g = 0; c < n_clips; ++c) {
-        const int64_t n = clip_len(c);
-        const int64_t F = num_frames(n, hop);
-        ClipDesc &d = e->h_desc.p[c];
-        while (c == gstart[g + 1]) ++g;
-        if (c == gstart[g]) gfirst[g] = frames;
-        if (loc == AID_PCM_DEVICE) {
-            // odd: K1's float2 frame loads are then 4-byte aligned (dword alignment suffices); s16 pairs 2-byte
-            d.pcm_off = offsets[c];
-        } else {
-            d.pcm_off = offsets[c] - offsets[0];  // the clips' span is staged as one copy
-            staged = offsets[c] + n - offsets[0];
-        }
-        d.frames = F;
-        d.frame_base = frames;
-        d.strip_base = gstrips[g];  // within the clip's group (K2 runs per group)
-        d.chunk_base = chunks;
-        d.hash_base = recs;
-        d.hash_cap = hash_capacity(F);
-        d.stft_base = kstrips;
-        e->clip_base[c] = recs;
-        e->clip_frames[c] = F;
-        empty_clip |= F == 0;
-        const int64_t nck = (F + kHashChunk - 1) / kHashChunk;
-        multi_chunk |= nck > 1;
-        one_chunk_each &= nck == 1;
-        frames += F;
-        gframes[g] += F;
-        gstrips[g] += (F + glen[g] - 1) / glen[g];
-        strips += (F + glen[g] - 1) / glen[g];
-        chunks += (F + kHashChunk - 1) / kHashChunk;
-        recs += d.hash_cap;
-        gk[g] += (F + kStftStrip - 1) / kStftStrip;
-        kstrips += (F + kStftStrip - 1) / kStftStrip;
-    }
-    HIP_TRY(e->desc.reserve((size_t)n_clips + 1));
-    HIP_TRY(e->power.reserve((size_t)std::max<int64_t>(1, *std::max_element(gframes.begin(), gframes.end())) * kBins));
-    HIP_TRY(e->mask.reserve((size_t)frames * kMaskWords));
-    HIP_TRY(e->hotw.reserve((size_t)frames + 1));
-    // relative mode: the clips' maxima start at +0 on this call's stream, ahead of the first group's K1 (ordered
-    // against earlier calls on other streams as hotw and mask are, by the stream wait above)
-    const bool rel = e->cfg.peak_rel > 0.0f;
-    if (rel) {
-        HIP_TRY(e->clip_qmax.reserve((size_t)n_clips + 1));
-        if (n_clips > 0) HIP_TRY(hipMemsetAsync(e->clip_qmax.p, 0, sizeof(uint32_t) * (size_t)n_clips, s));
-    }
-    if (!e->k2_cold.p) {
-        HIP_TRY(e->k2_cold.reserve(128));
-        HIP_TRY(hipMemsetAsync(e->k2_cold.p, 0, 128 * sizeof(uint32_t), s));
-    }
-    if (!e->h_cold.p) {
-        HIP_TRY(e->h_cold.reserve(2, hipHostMallocMapped));
-        e->h_cold.p[0] = e->h_cold.p[1] = 0;
-        HIP_TRY(hipHostGetDevicePointer((void **)&e->h_cold_dev, e->h_cold.p, 0));
-    }
-    HIP_TRY(e->chunk_counts.reserve((size_t)chunks + 1));
-    HIP_TRY(e->records.reserve((size_t)recs + 1));
-    HIP_TRY(e->counts.reserve((size_t)n_clips + 1));
-    const void *dpcm = pcm;
-    if (loc == AID_PCM_HOST && staged > 0) {
-        // K1 of an earlier call may still read the staging buffer: on the same stream the new copy is ordered after
-        // it (a pipelined submit must not wait for the previous batch's K1), on another stream the host waits
-        if (e->stage_stream != s) HIP_TRY(e->stage_ev.wait());
-        e->stage_ev.live = false;
-        // one copy of the clips' whole span (clips at odd offsets are read with dword-aligned float2 loads; a copy
-        // per clip cost ~10-20 us of call overhead each: 64 coalesced service queries ~1 ms)
-        // the staging buffer is raw bytes to both formats (s16: half the copy); stage_ev orders its reuse across them
-        const size_t nbytes = (size_t)staged * pcm_size(fmt);
-        HIP_TRY(e->pcm_stage.reserve((nbytes + sizeof(float) - 1) / sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(e->pcm_stage.p, pcm_at(pcm, fmt, offsets[0]), nbytes, hipMemcpyHostToDevice, s));
-        dpcm = e->pcm_stage.p;
-    }
-    if (n_clips > 0 && !desc_same) {
-        HIP_TRY(hipMemcpyAsync(e->desc.p, e->h_desc.p, sizeof(ClipDesc) * n_clips, hipMemcpyHostToDevice, s));
-        HIP_TRY(e->desc_ev.record(s));
-        e->desc_key.resize(2 * (size_t)n_clips);
-        for (int c = 0; c < n_clips; ++c) {
-            e->desc_key[2 * c] = offsets[c];
-            e->desc_key[2 * c + 1] = clip_len(c);
-        }
-        e->desc_key.push_back(loc);
-        for (int g = 0; g < n_groups; ++g) {
-            e->desc_key.push_back(gstart[g]);
-            e->desc_key.push_back(glen[g]);
-        }
-        e->desc_key.push_back(width);
-        e->desc_dev_for_key = e->desc.p;
-    }
-    if (empty_clip || frames == 0) HIP_TRY(hipMemsetAsync(e->counts.p, 0, sizeof(int64_t) * ((size_t)n_clips + 1), s));
-    e->n_clips = n_clips;
-    e->total_frames = frames;
-    e->total_strips = strips;
-    e->total_chunks = chunks;
-    e->total_records = recs;
-    if (frames > 0) {
-        for (int g = 0; g < n_groups; ++g) {  // K1 -> K2 per clip group, on one power buffer
-            const int ca = gstart[g], ng = gstart[g + 1] - ca;
-            if (gframes[g] == 0) continue;
-            {
-                ProfScope ps(e, AID_K_STFT, s, true);
-                launch_stft_power(dpcm, fmt == kS16, e->desc.p + ca, ng, gfirst[g], gframes[g], gk[g], e->k1_slots, hop, e->d_tab.p,
-                                  e->power.p, false, e->hotw.p, e->cfg.peak_threshold,
-                                  (e->cfg.flags & AID_FLAG_KEEP_POWER) != 0, rel ? e->clip_qmax.p + ca : nullptr, s);
-            }
-            if (loc == AID_PCM_HOST && g == n_groups - 1) {
-                HIP_TRY(e->stage_ev.record(s));
-                e->stage_stream = s;
-            }
-            {
-                ProfScope ps(e, AID_K_PEAKS, s, true);
-                launch_peak_pick(width, e->power.p, e->desc.p + ca, ng, gfirst[g], gstrips[g], glen[g], e->cfg.peak_threshold,
-                                 e->hotw.p, e->mask.p, e->k2_cold.p, rel ? e->clip_qmax.p + ca : nullptr,
-                                 e->cfg.peak_rel, s);
-            }
-        }
-        if (multi_chunk) {  // some clip spans several K3 chunks: their bases need the COUNT pass
-            ProfScope ps(e, AID_K_LANDMARK_COUNT, s, true);
-            launch_landmarks(e->mask.p, e->desc.p, n_clips, chunks, e->chunk_counts.p, e->records.p, e->counts.p,
-                             false, nullptr, nullptr, 0u, 0u, one_chunk_each, s);
-        }
-        {
-            ProfScope ps(e, AID_K_LANDMARK_WRITE, s, true);
-            launch_landmarks(e->mask.p, e->desc.p, n_clips, chunks, e->chunk_counts.p, e->records.p, e->counts.p,
-                             true, e->h_cold_dev ? e->k2_cold.p : nullptr, e->h_cold_dev, (uint32_t)(width * strips),
-                             (uint32_t)strips, one_chunk_each, s);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    e->last_stream = s;
-    e->have_result = true;
-    return AID_OK;
-}
-
-int aid_sync(aid_engine *e) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->last_stream ? e->last_stream : e->own_stream));
-    return AID_OK;
-}
-
-int aid_result_counts(aid_engine *e, int64_t *counts) {
-    if (!e || (!counts && e->n_clips > 0)) return fail(AID_ERR_INVALID, "null argument");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (int rc = aid_sync(e)) return rc;
-    if (e->n_clips > 0) HIP_TRY(hipMemcpy(counts, e->counts.p, sizeof(int64_t) * e->n_clips, hipMemcpyDeviceToHost));
-    return AID_OK;
-}
-
-int aid_result_hashes(aid_engine *e, int32_t clip, aid_hash *out, int64_t cap, int64_t *n_out) {
-    if (!e || !n_out) return fail(AID_ERR_INVALID, "null argument");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (clip < 0 || clip >= e->n_clips) return fail(AID_ERR_INVALID, "clip index out of range");
-    if (int rc = aid_sync(e)) return rc;
-    int64_t n = 0;
-    HIP_TRY(hipMemcpy(&n, e->counts.p + clip, sizeof(int64_t), hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n > cap) return fail(AID_ERR_INVALID, "output capacity too small");
-    if (n > 0) {
-        if (!out) return fail(AID_ERR_INVALID, "null output");
-        HIP_TRY(hipMemcpy(out, e->records.p + e->clip_base[clip], n * sizeof(aid_hash), hipMemcpyDeviceToHost));
-    }
-    return AID_OK;
-}
-
-int aid_result_device(aid_engine *e, const aid_hash **records, const int64_t **counts_dev,
-                      const int64_t **clip_base_host, int32_t *n_clips) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (records) *records = reinterpret_cast<const aid_hash *>(e->records.p);
-    if (counts_dev) *counts_dev = e->counts.p;
-    if (clip_base_host) *clip_base_host = e->clip_base.data();
-    if (n_clips) *n_clips = e->n_clips;
-    return AID_OK;
-}
-
-int aid_result_power(aid_engine *e, int32_t clip, float *out, int64_t cap) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (clip < 0 || clip >= e->n_clips) return fail(AID_ERR_INVALID, "clip index out of range");
-    if (!(e->cfg.flags & AID_FLAG_KEEP_POWER))
-        return fail(AID_ERR_STATE, "aid_result_power: engine created without AID_FLAG_KEEP_POWER (cold blocks not stored)");
-    const int64_t F = e->clip_frames[clip];
-    if (F * kBins > cap) return fail(AID_ERR_INVALID, "output capacity too small");
-    if (int rc = aid_sync(e)) return rc;
-    if (F > 0) {
-        int64_t fb = 0;
-        for (int c = 0; c < clip; ++c) fb += e->clip_frames[c];
-        HIP_TRY(hipMemcpy(out, e->power.p + fb * kBins, F * kBins * sizeof(float), hipMemcpyDeviceToHost));
-        // K1 stores Q = fma(Xr, Xr, Xi*Xi) = 4P; FPSPEC 4's P is Q * 0.25f, the same binary32 op
-        for (int64_t i = 0; i < F * kBins; ++i) out[i] = out[i] * 0.25f;
-    }
-    return AID_OK;
-}
-
-int aid_result_thresholds(aid_engine *e, float *out) {
-    if (!e || (!out && e->n_clips > 0)) return fail(AID_ERR_INVALID, "null argument");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (int rc = aid_sync(e)) return rc;
-    const float thr = e->cfg.peak_threshold, r = e->cfg.peak_rel;
-    if (!(r > 0.0f) || e->n_clips == 0) {
-        for (int c = 0; c < e->n_clips; ++c) out[c] = thr;
-        return AID_OK;
-    }
-    std::vector<uint32_t> q((size_t)e->n_clips);
-    HIP_TRY(hipMemcpy(q.data(), e->clip_qmax.p, sizeof(uint32_t) * q.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < e->n_clips; ++c) {
-        // FPSPEC 5.1 in the spec's own terms: Pmax = Qmax * 0.25f (the readout scaling of aid_result_power; the
-        // maximum commutes with it), one binary32 multiply by r, then the maximum with the floor
-        float qm;
-        std::memcpy(&qm, &q[c], sizeof(qm));
-        const float t = r * (qm * 0.25f);
-        out[c] = t > thr ? t : thr;
-    }
-    return AID_OK;
-}
-
-int aid_result_peakmask(aid_engine *e, int32_t clip, uint64_t *out, int64_t cap) {
-    if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction yet");
-    if (clip < 0 || clip >= e->n_clips) return fail(AID_ERR_INVALID, "clip index out of range");
-    const int64_t F = e->clip_frames[clip];
-    if (F * kMaskWords > cap) return fail(AID_ERR_INVALID, "output capacity too small");
-    if (int rc = aid_sync(e)) return rc;
-    if (F > 0) {
-        int64_t fb = 0;
-        for (int c = 0; c < clip; ++c) fb += e->clip_frames[c];
-        HIP_TRY(hipMemcpy(out, e->mask.p + fb * kMaskWords, F * kMaskWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return AID_OK;
-}
-
-int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int64_t cap) {
-    if (!e || (n > 0 && !pcm) || n < 0) return fail(AID_ERR_INVALID, "aid_spectrogram: bad argument");
-    const int64_t F = num_frames(n, e->cfg.hop);
-    if (F * kBins > cap) return fail(AID_ERR_INVALID, "output capacity too small");
-    if (F == 0) return AID_OK;
-    EngineCall call(e, nullptr, false, kDrainLast);
-    if (call.rc) return call.rc;
-    hipStream_t s = call.s;
-    DevBuf<float> d_pcm, d_out;
-    DevBuf<ClipDesc> d_desc;
-    ClipDesc d{};
-    d.frames = F;
-    HIP_TRY(d_pcm.reserve((size_t)n));
-    // from here every failure is AID_ERR_DEVICE under the function's name
-    auto ok = [](hipError_t he) {
-        return he == hipSuccess ? AID_OK : fail(AID_ERR_DEVICE, std::string("aid_spectrogram: ") + hipGetErrorString(he));
-    };
-    if (int rc = ok(d_out.reserve((size_t)(F * kBins)))) return rc;
-    if (int rc = ok(d_desc.reserve(1))) return rc;
-    if (int rc = ok(hipMemcpy(d_pcm.p, pcm, n * sizeof(float), hipMemcpyHostToDevice))) return rc;
-    if (int rc = ok(hipMemcpy(d_desc.p, &d, sizeof(ClipDesc), hipMemcpyHostToDevice))) return rc;
-    launch_stft_power(d_pcm.p, false, d_desc.p, 1, 0, F, (F + kStftStrip - 1) / kStftStrip, e->k1_slots, e->cfg.hop,
-                      e->d_tab.p, d_out.p, true, nullptr, e->cfg.peak_threshold, true, nullptr, s);
-    if (int rc = ok(hipGetLastError())) return rc;
-    if (int rc = ok(hipStreamSynchronize(s))) return rc;
-    return ok(hipMemcpy(out, d_out.p, F * kBins * sizeof(float), hipMemcpyDeviceToHost));
 }
 
 int aid_synth_rate(aid_engine *e, float *dst, const uint32_t *tracks, const int64_t *starts, int32_t n_clips,
@@ -1021,7 +625,7 @@ int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
     const int64_t v[15] = {e->st_queries,     e->st_votes,   e->st_post_reads, e->st_q_lds,
                            e->st_q_global,    e->st_records, e->st_sig_reads,  (int64_t)match_lds_blocks_per_cu(),
                            e->st_fb_reason[0], e->st_fb_reason[1], e->st_fb_reason[2], e->st_fb_reason[3],
-                           e->st_fb_reason[4], e->k2_width, e->total_strips};
+                           e->st_fb_reason[4], e->ext.k2.width, e->ext.plan.strips};
     for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
     if (reset) {
         e->st_queries = e->st_votes = e->st_post_reads = e->st_q_lds = e->st_q_global = e->st_records = e->st_sig_reads = 0;

@@ -1,9 +1,9 @@
 // engine_internal.h -- what the host files of libaidfp.so share: the engine's state (struct aid_engine), its buffer
 // and profiling helpers, the prologue of its entry points (EngineCall), and the few functions the host files call
-// across their boundaries. engine.cpp: the engine itself, extraction, resampling, dedup, the vector lane's wrappers,
-// profiling. index_host.cpp: the hash index (aidfp_index.h). index_exchange.cpp: aid_comm and the index exchange
-// (the only file that includes RCCL). query.cpp: K5, the query entry points, the exact lane. Nothing here is part
-// of the C ABI.
+// across their boundaries. engine.cpp: the engine itself, synth, resampling, dedup, the vector lane's wrappers,
+// profiling. extract.cpp: extraction and its results (aidfp_extract.h). index_host.cpp: the hash index
+// (aidfp_index.h). index_exchange.cpp: aid_comm and the index exchange (the only file that includes RCCL).
+// query.cpp: K5, the query entry points, the exact lane. Nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "../../include/aidfp.h"
 #include "aidfp_buffers.h"
 #include "aidfp_device.h"
+#include "aidfp_extract.h"
 #include "aidfp_index.h"
 #include "aidfp_launch.h"
 #include "aidfp_layout.h"
@@ -79,29 +80,9 @@ struct aid_engine {
     aid_config cfg{};
     int device = 0;
     OwnStream own_stream;
+    Extractor ext;  // extraction (FPSPEC 1-6): K1..K3's buffers, K2's policy, the last call's plan (aidfp_extract.h)
     DevBuf<Tables> d_tab;
     DevBuf<int16_t> d_sin;
-
-    DevBuf<float> pcm_stage;
-    DevBuf<float> power;
-    DevBuf<uint64_t> mask;
-    DevBuf<uint64_t> hotw;  // K1 -> K2: per power row, bit hot_bit(c) = 16-bin chunk c has a value > thr
-    // FPSPEC 5.1 (cfg.peak_rel > 0): per clip of the call, the bit pattern of max Q over its plane. Zeroed on the
-    // call's stream before the first K1, raised by K1's atomics, read by K2 and aid_result_thresholds
-    DevBuf<uint32_t> clip_qmax;
-    DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3
-    // pinned, host-mapped, two words: K3 stores (cold waves | waves << 32) and (twice-walked strips | strips << 32) of
-    // the last K2 here; waves / strips is the width that K2 ran at
-    HostBuf<uint64_t> h_cold;
-    uint64_t *h_cold_dev = nullptr;  // its device address
-    int k2_width_force = 0;          // aid_engine_force K2_WIDTH: 2 or 4 quarter waves per K2 workgroup; 0 = adaptive
-    int k2_width = 4;                // the adaptive choice (extract_locked); also the width of the last call
-    int k2_hold = 0;                 // calls left at width 4 after a fall-back from width 2 (hysteresis)
-    double k2_slots_x = 0.0;         // aid_engine_force K2_STRIPS: fixed strips per slot; 0 = adaptive (extract_locked)
-    DevBuf<ClipDesc> desc;
-    DevBuf<int64_t> chunk_counts;
-    DevBuf<uint64_t> records;
-    DevBuf<int64_t> counts;
     DevBuf<uint32_t> synth_tracks;
     DevBuf<int64_t> synth_starts;
     HostBuf<uint8_t> h_synth;  // pinned staging of aid_synth_rate's tracks + starts (AID_SYNTH_ASYNC returns early)
@@ -140,32 +121,17 @@ struct aid_engine {
     VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
     size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero
 
-    HostBuf<ClipDesc> h_desc;  // pinned
-    // extraction call hazards, tracked with events instead of a stream sync per call:
-    // h_desc is the source of an async H2D copy; pcm_stage is read by K1
-    Event desc_ev, stage_ev;
-    hipStream_t stage_stream = nullptr;  // the stream whose K1 read pcm_stage last
-    std::vector<int64_t> desc_key;  // offsets (+ pcm location) the device descriptors were built for
-    ClipDesc *desc_dev_for_key = nullptr;
-    std::vector<int64_t> clip_base;  // host copy of desc[c].hash_base
-    std::vector<int64_t> clip_frames;
-    int n_clips = 0;
-    int64_t total_frames = 0, total_strips = 0, total_chunks = 0, total_records = 0;
-    int64_t k2_slots[2] = {1, 1};  // resident K2 workgroups on the device (CUs x blocks per CU) at width 2, 4
-    int64_t k1_slots = 1;  // resident K1 waves (CUs x kStftWaves: one K1 workgroup per CU)
     // aid_engine_force K5_PATH (tests): 0 the LDS pass, then the global path for the queries it hands back; 1 as 0
     // (kept for callers that pin the LDS path); 2 global path only. The submit/collect pair ignores it
     int k5_path = 0;
     int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
     int lane_gather = 0;           // aid_engine_force LANE_GATHER: stage the exact lane's sub-windows (A/B)
-    int64_t plane_rows = 0;        // aid_engine_force PLANE_ROWS: power rows per K1 -> K2 clip group (0 = kPlaneRows)
     // aid_match_stats: queries, exact votes, and the postings K5 read (a vote = one 8-B posting per pass)
     int64_t st_queries = 0, st_votes = 0, st_post_reads = 0, st_q_global = 0, st_q_lds = 0, st_records = 0;
     int64_t st_sig_reads = 0;  // 2-B posting signatures the LDS path read (two per vote: counting and insert passes)
     int64_t st_fb_reason[5] = {0, 0, 0, 0, 0};  // LDS-path fallbacks (speculative pass) by reason (index.hip)
     size_t k5_batch = 2048;        // global-path queries per launch
     hipStream_t last_stream = nullptr;
-    bool have_result = false;
 
     bool profiling = false;
     uint32_t prof_mask = 0xFFFFFFFFu;  // bit k: kernel id k gets events (aid_profile_select)
@@ -306,8 +272,8 @@ struct EngineCall {
     }
 };
 
-// engine lock held; defined among engine.cpp's extern "C" functions, hence the linkage
-extern "C" int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                              int32_t loc, void *stream, const int64_t *ends = nullptr);
+// extract.cpp; engine lock held
+int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                   void *stream, const int64_t *ends = nullptr);
 
 #pragma GCC visibility pop

@@ -82,14 +82,14 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     if (!e) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad argument");
     EngineCall call(e);
     if (call.rc) return call.rc;
-    if (!track_ids && e->n_clips > 0) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad argument");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction to index");
+    if (!track_ids && e->ext.plan.n_clips > 0) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad argument");
+    if (!e->ext.have_result) return fail(AID_ERR_STATE, "no extraction to index");
     // 0xFFFFFFFF is K5's empty-slot marker (and track + 1 would wrap to 0 below), as in aid_index_add_track
-    for (int c = 0; c < e->n_clips; ++c)
+    for (int c = 0; c < e->ext.plan.n_clips; ++c)
         if (track_ids[c] == 0xFFFFFFFFu) return fail(AID_ERR_INVALID, "aid_index_add_extracted: bad track id");
     HashIndex &ix = e->idx;
     hipStream_t s = e->last_stream ? e->last_stream : call.s;  // behind the extraction, without waiting for it
-    const int n = e->n_clips;
+    const int n = e->ext.plan.n_clips;
     if (n == 0) return AID_OK;
     // the previous call's count (normally long arrived: this batch's extraction was queued behind it) and its
     // pinned staging, whose H2D copies precede that call's event
@@ -100,7 +100,7 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     uint32_t *trk = reinterpret_cast<uint32_t *>(dst + n);
     uint32_t mx = 0;
     for (int c = 0; c < n; ++c) {
-        src[c] = e->clip_base[c];
+        src[c] = e->ext.plan.hash_base[c];
         trk[c] = track_ids[c];
         mx = std::max(mx, track_ids[c] + 1);
     }
@@ -113,22 +113,22 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     // to the exact need plus one batch's hash capacity (1.5x the records buffer the extraction already holds),
     // so the following appends of such batches are asynchronous again (growth doubles: this path runs
     // O(log n) times), unless that headroom would take more than a quarter of the free device memory
-    const int64_t bound = e->total_records;
+    const int64_t bound = e->ext.plan.records;
     const int64_t cap = (int64_t)std::min({ix.p_hash.n, ix.p_track.n, ix.p_t.n});
     if (ix.n_post + bound <= cap) {
         HIP_TRY(ix.h_npost.reserve(1));
         HIP_TRY(ix.d_npost.reserve(1));
         HIP_TRY(hipMemcpyAsync(ix.x_src.p, src, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(ix.x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        launch_append_offsets(e->counts.p, n, ix.n_post, ix.x_dst.p, ix.d_npost.p, s);
-        launch_records_to_postings(e->records.p, ix.x_src.p, e->counts.p, ix.x_dst.p, ix.x_tracks.p, n, ix.p_hash.p,
+        launch_append_offsets(e->ext.counts.p, n, ix.n_post, ix.x_dst.p, ix.d_npost.p, s);
+        launch_records_to_postings(e->ext.records.p, ix.x_src.p, e->ext.counts.p, ix.x_dst.p, ix.x_tracks.p, n, ix.p_hash.p,
                                    ix.p_track.p, ix.p_t.p, s);
         HIP_TRY(hipMemcpyAsync(ix.h_npost.p, ix.d_npost.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(ix.add_ev.record(s));
         HIP_TRY(hipGetLastError());
         ix.post_pend = true;
     } else {
-        HIP_TRY(hipMemcpyAsync(counts, e->counts.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(counts, e->ext.counts.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         int64_t tot = 0;
         for (int c = 0; c < n; ++c) {
@@ -142,7 +142,7 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
         HIP_TRY(hipMemcpyAsync(ix.x_src.p, src, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(ix.x_dst.p, dst, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(ix.x_tracks.p, trk, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        launch_records_to_postings(e->records.p, ix.x_src.p, e->counts.p, ix.x_dst.p, ix.x_tracks.p, n, ix.p_hash.p,
+        launch_records_to_postings(e->ext.records.p, ix.x_src.p, e->ext.counts.p, ix.x_dst.p, ix.x_tracks.p, n, ix.p_hash.p,
                                    ix.p_track.p, ix.p_t.p, s);
         HIP_TRY(ix.add_ev.record(s));  // the staging's copies (the next call waits for them)
         HIP_TRY(hipGetLastError());  // no sync: every reader of the posting planes syncs last_stream first

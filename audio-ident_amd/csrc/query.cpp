@@ -1,5 +1,5 @@
 // query.cpp -- the query half of libaidfp.so's host side: K5's orchestration, the query entry points (synchronous,
-// and the submit / collect pair with its tickets) and the batched exact lane. Extraction lives in engine.cpp, the
+// and the submit / collect pair with its tickets) and the batched exact lane. Extraction lives in extract.cpp, the
 // index in index_host.cpp (K5 reads it through HashIndex::view()); engine_internal.h is what the host files share.
 #include <hip/hip_runtime.h>
 
@@ -201,8 +201,8 @@ static int run_queries(aid_engine *e, const uint64_t *recs, const int64_t *qstar
 // stay below 2^20 - 1 (3.4 h of audio at 44.1 kHz, 4.6 h at 16 kHz)
 constexpr int64_t kMaxQueryFrame = ((int64_t)1 << 20) - 2;
 static int check_query_frames(const aid_engine *e) {
-    for (int c = 0; c < e->n_clips; ++c)
-        if (e->clip_frames[c] > kMaxQueryFrame + 1)
+    for (int c = 0; c < e->ext.plan.n_clips; ++c)
+        if (e->ext.plan.frames[c] > kMaxQueryFrame + 1)
             return fail(AID_ERR_INVALID, "query clip longer than 2^20 - 1 frames (FPSPEC v1 7)");
     return AID_OK;
 }
@@ -242,7 +242,7 @@ int aid_query(aid_engine *e, const aid_hash *recs, const int64_t *qoff, int32_t 
 static hipError_t upload_clip_base(aid_engine *e, int n, hipStream_t s) {
     hipError_t he = e->hq_start.reserve((size_t)n);
     if (he != hipSuccess) return he;
-    std::memcpy(e->hq_start.p, e->clip_base.data(), (size_t)n * sizeof(int64_t));
+    std::memcpy(e->hq_start.p, e->ext.plan.hash_base.data(), (size_t)n * sizeof(int64_t));
     return hipMemcpyAsync(e->q_start.p, e->hq_start.p, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s);
 }
 
@@ -250,17 +250,17 @@ static int query_extracted_locked(aid_engine *e, aid_match_row *rows, int32_t *n
     if (int rc = check_query_frames(e)) return rc;
     if (int rc = ensure_index(e)) return rc;
     hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
-    const int nq = e->n_clips;
+    const int nq = e->ext.plan.n_clips;
     if (nq == 0) return AID_OK;
     if (!rows || !nrows) return fail(AID_ERR_INVALID, "null output");
     HIP_TRY(e->q_start.reserve(nq));
     HIP_TRY(upload_clip_base(e, nq, s));
-    return run_queries(e, e->records.p, e->q_start.p, e->counts.p, nq, (int64_t)e->records.n, rows, nrows, s);
+    return run_queries(e, e->ext.records.p, e->q_start.p, e->ext.counts.p, nq, (int64_t)e->ext.records.n, rows, nrows, s);
 }
 
 int aid_query_extracted(aid_engine *e, aid_match_row *rows, int32_t *nrows) {
     if (!e) return fail(AID_ERR_INVALID, "null engine");
-    if (!e->have_result) return fail(AID_ERR_STATE, "no extraction to query with");
+    if (!e->ext.have_result) return fail(AID_ERR_STATE, "no extraction to query with");
     std::lock_guard<std::mutex> lk(e->mu);
     return query_extracted_locked(e, rows, nrows);
 }
@@ -312,15 +312,15 @@ static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64
     hipStream_t s = e->last_stream ? e->last_stream : e->own_stream;
     t->s = s;
     const int nq = n;
-    t->nrec = e->clip_base[nq - 1] + hash_capacity(e->clip_frames[nq - 1]);
+    t->nrec = e->ext.plan.records;
     HIP_TRY(t->host.meta.reserve((size_t)3 * nq));
     HIP_TRY(t->recs.reserve((size_t)std::max<int64_t>(t->nrec, 1)));
     HIP_TRY(t->qsc.reserve((size_t)2 * nq));
-    std::memcpy(t->host.meta.p, e->clip_base.data(), (size_t)nq * sizeof(int64_t));
+    std::memcpy(t->host.meta.p, e->ext.plan.hash_base.data(), (size_t)nq * sizeof(int64_t));
     // the ticket's own copies: record starts (from its page-locked meta), counts and records (device to device)
     HIP_TRY(hipMemcpyAsync(t->qsc.p, t->host.meta.p, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t->qsc.p + nq, e->counts.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t->recs.p, e->records.p, (size_t)t->nrec * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t->qsc.p + nq, e->ext.counts.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t->recs.p, e->ext.records.p, (size_t)t->nrec * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     // always the LDS pass: a ticket ignores the K5_PATH force (collect runs the global path for what it hands back)
     if (int rc = k5_enqueue(e, t->recs.p, t->qsc.p, t->qsc.p + nq, nq, t->nrec, true, true, t->host, s, true)) return rc;
     HIP_TRY(t->ev.record(s));
@@ -566,8 +566,8 @@ static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const i
         if (int rc = check_query_frames(e)) return rc;
         HIP_TRY(e->q_start.reserve(n_win));
         HIP_TRY(upload_clip_base(e, n_win, s));
-        if (int rc = run_queries(e, e->records.p, e->q_start.p, e->counts.p, n_win, (int64_t)e->records.n, nullptr,
-                                 nrows.data(), s))
+        if (int rc = run_queries(e, e->ext.records.p, e->q_start.p, e->ext.counts.p, n_win,
+                                 (int64_t)e->ext.records.n, nullptr, nrows.data(), s))
             return rc;
         HIP_TRY(e->q_nrows.reserve((size_t)n_win));
         HIP_TRY(hipMemcpyAsync(e->q_nrows.p, nrows.data(), n_win * sizeof(int32_t), hipMemcpyHostToDevice, s));

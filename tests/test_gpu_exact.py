@@ -109,7 +109,7 @@ def test_device_pcm_and_many_clips(service):
 
 
 def test_lane_rows_under_clip_groups(service):
-    """The lane's windows split into several K1 -> K2 groups (engine.cpp extract_locked; `plane_rows` forces a
+    """The lane's windows split into several K1 -> K2 groups (extract.cpp extract_locked; `plane_rows` forces a
     small bound) give the same rows as one group."""
     base = clips()[3:12]
     many = [base[i % len(base)] for i in range(120)]

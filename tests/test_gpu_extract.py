@@ -219,6 +219,54 @@ def test_back_to_back_calls_without_sync(gpu_engine):
     assert counts[1] == 0  # the 1000-sample clip has no frame
 
 
+@pytest.mark.parametrize("first", [0, 2])
+def test_descriptor_cache_without_sync(first):
+    """The descriptor upload is skipped exactly when the planned descriptors equal the ones last uploaded
+    (aidfp_extract_plan.h desc_differ): one engine, calls queued with no sync but the result reads: the same device
+    batch twice (cached), after a forced strip multiplier (100 -> 300: these clips keep the 16-frame strip floor, so
+    the descriptors stay equal and the call is cached too) and a forced plane bound (the groups, so the strip bases,
+    change), then host PCM and the device batch again. With the device clips from sample 0 the host call plans the
+    very descriptors already uploaded (only the PCM pointer differs, a kernel argument) and uploads none; from
+    sample 2 every pcm_off differs. Then one group again and 0.01 strips per slot: strips longer than the floor, so
+    the strip bases move with nothing but the multiplier. Counts after each forced step and the hashes after the
+    sixth and the last call are the oracle's."""
+    import torch
+    from aidfp.engine import AID_PCM_HOST, Engine, _p
+
+    a = [_clip(40 + i, n, start=31 * i) for i, n in enumerate([44100 * 3, 30000, 44100 * 2])]
+    ref = [O.fingerprint(x, HOP) for x in a]
+    want = [len(r) for r in ref]
+    offs = first + np.concatenate([[0], np.cumsum([len(x) for x in a])]).astype(np.int64)
+    host = np.concatenate(a).astype(np.float32)
+    dev = torch.zeros(int(offs[-1]), dtype=torch.float32, device="cuda")
+    dev[first:] = torch.from_numpy(host)
+    torch.cuda.synchronize()
+    s = torch.cuda.current_stream().cuda_stream
+    with Engine(SR) as eng:
+        eng.force("k2_strips_x100", 100)
+        eng.extract_device(dev.data_ptr(), offs, s)
+        eng.extract_device(dev.data_ptr(), offs, s)  # the cached case
+        eng.force("k2_strips_x100", 300)
+        eng.extract_device(dev.data_ptr(), offs, s)
+        assert eng.counts().tolist() == want, "after k2_strips_x100 300"
+        eng.force("plane_rows", 1)
+        eng.extract_device(dev.data_ptr(), offs, s)
+        assert eng.counts().tolist() == want, "after plane_rows 1"
+        hoffs = offs - first
+        # the C entry itself: Engine.extract_host would fetch (and wait for) the hashes
+        assert eng._lib.aid_extract(eng._h, _p(host), _p(hoffs), len(a), AID_PCM_HOST, s or None) == 0
+        eng.extract_device(dev.data_ptr(), offs, s)
+        for c in range(len(a)):
+            assert np.array_equal(eng.hashes(c), ref[c]), f"clip {c}"
+        eng.force("plane_rows", 0)
+        eng.extract_device(dev.data_ptr(), offs, s)
+        eng.force("k2_strips_x100", 1)
+        eng.extract_device(dev.data_ptr(), offs, s)
+        assert eng.counts().tolist() == want, "after k2_strips_x100 1"
+        for c in range(len(a)):
+            assert np.array_equal(eng.hashes(c), ref[c]), f"clip {c} after k2_strips_x100 1"
+
+
 @pytest.mark.parametrize("keep", [False, True])
 @pytest.mark.parametrize("hop", [128, 256, 1024, 2048])
 def test_every_hop_bit_exact(hop, keep):
@@ -329,7 +377,7 @@ def test_band_limited_quarters_bit_exact(gpu_engine):
 @pytest.mark.parametrize("slots_x", ["1", "1.25", "1.5", "3"])
 def test_k2_strip_multipliers_bit_exact(slots_x):
     """K2's strip count follows the measured cold-wave fraction (1, 1.25 or 1.5 strips per resident
-    workgroup slot, engine.cpp extract_locked; strip-cold waves exit). Every fixed multiplier, including
+    workgroup slot, aidfp_extract_plan.h K2Policy; strip-cold waves exit). Every fixed multiplier, including
     one that leaves workgroups waiting for slots, gives the oracle's peaks and hashes bit for bit, on a
     band-limited batch where about half of the quarter waves are strip-cold and exit."""
     from aidfp.engine import Engine
@@ -346,11 +394,11 @@ def test_k2_strip_multipliers_bit_exact(slots_x):
 
 @pytest.mark.parametrize("rows", [0, 1, 700, 2000])
 def test_clip_groups_bit_exact(rows):
-    """A call whose frames exceed the plane bound runs K1 -> K2 per group of clips on one power buffer (engine.cpp
+    """A call whose frames exceed the plane bound runs K1 -> K2 per group of clips on one power buffer (extract.cpp
     extract_locked, kPlaneRows; `plane_rows` forces the bound). Every grouping gives the oracle's peaks and hashes:
     a group per clip (1), several clips per group with a clip longer than the bound alone in its group (700, 2000
     rows; the 40 s clip has 3,445 frames), and one group (0); host and device PCM, and calls repeated (cached
-    descriptors keyed on the groups)."""
+    descriptors: the second call uploads none)."""
     import torch
 
     from aidfp.engine import Engine
