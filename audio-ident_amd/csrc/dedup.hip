@@ -7,7 +7,10 @@
 //
 // Exactness: the score is computed in binary64 with the reference's operation order,
 // (matching / (min_len*32)) * (min_len / max_len), each op correctly rounded, so it equals
-// the Python float bit for bit (tests/test_gpu_dedup.py vs tests/golden/ref_dedup.json).
+// the Python float bit for bit (tests/test_gpu_dedup.py vs tests/golden/ref_dedup.json; tests/test_gpu_dedup_edges.py
+// vs oracle/fp_dedup.c on the constructed catalogs of tests/dedup_fixtures.py: ties and one-bit near ties within a
+// wave, across waves and chunks, lengths around the wave stride, the band's bounds, adds in pieces; the builders'
+// own preconditions: tests/test_dedup_fixtures_host.py).
 //
 // Layout: catalog words u32 concatenated (offsets i64[n+1]) + durations f64[n]; queries the
 // same. Grid (query, chunk of 64 entries) with the query index fastest, so the workgroups in
@@ -120,7 +123,7 @@ void launch_dedup_scan(const uint32_t *cw, const int64_t *coff, const double *cd
                        int64_t *part_idx, double *best_sim, int64_t *best_idx, hipStream_t s) {
     if (nq <= 0) return;
     const int nc = dedup_chunks(n_cat);
-    if (nc > 0)
+    if (nc > 0)  // nc is grid.y: above 65,535 chunks (4,194,240 entries) the launch fails and the caller gets the error
         hipLaunchKernelGGL(k_dedup_scan, dim3((unsigned)nq, (unsigned)nc), dim3(256), 0, s, cw, coff, cdur, n_cat, qw,
                            qoff, qlo, qhi, nq, part_sim, part_idx, nc);
     hipLaunchKernelGGL(k_dedup_final, dim3((unsigned)nq), dim3(64), 0, s, part_sim, part_idx, nc, best_sim, best_idx);

@@ -16,6 +16,12 @@
 // `window_gather`, which copies each sub-window to an even offset of a staging buffer first, is
 // the A/B behind aid_engine_force(LANE_GATHER). K8b `exact_consensus` runs one wave per clip over
 // the K5 rows of its windows (<= 3 x max_results rows, staged in LDS).
+//
+// Tests: tests/test_gpu_exact.py, tests/test_gpu_lane_parity.py and tests/test_gpu_s16_service.py (the lane against
+// the per-window path on synthesised audio); tests/test_gpu_consensus_edges.py (K8b's decision edges on the
+// constructed index of tests/consensus_fixtures.py against the all-oracle lane: 7 / 8 aligned hashes, halving,
+// medians, confidence ties cut by max_out, kExactMaxRows staged rows; the builder's own preconditions:
+// tests/test_consensus_fixtures_host.py).
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
 

@@ -310,6 +310,13 @@ def _pack_u32(arrs):
     return np.ascontiguousarray(w), off
 
 
+def dedup_similarity(a, b) -> float:
+    """`_fingerprint_similarity` of two uint32 word arrays (fp_dedup_similarity), as a Python float."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    return float(lib().fp_dedup_similarity(_ptr(a), len(a), _ptr(b), len(b)))
+
+
 def dedup_scan(cat, cat_dur, queries, q_dur):
     """cat/queries: lists of uint32 arrays. Returns (best_idx int64[nq] (-1 = none), best_sim f64[nq])."""
     cw, co = _pack_u32(cat)
