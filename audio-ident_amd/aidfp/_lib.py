@@ -24,11 +24,12 @@ AID_SYNTH_STATIONARY = 1
 AID_SYNTH_ASYNC = 2
 (AID_FORCE_K5_PATH, AID_FORCE_K5_PARTS, AID_FORCE_K5_BATCH, AID_FORCE_K2_STRIPS_X100, AID_FORCE_K4_BUILD,
  AID_FORCE_EXCHANGE_FAIL, AID_FORCE_LANE_GATHER, AID_FORCE_PLANE_ROWS, AID_FORCE_K2_WIDTH) = 1, 2, 3, 4, 5, 6, 7, 8, 9
-AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK = 10, 11
+AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK, AID_FORCE_SPEED_GROUP = 10, 11, 12
 AID_K_STFT, AID_K_PEAKS, AID_K_LANDMARK_COUNT, AID_K_LANDMARK_WRITE, AID_K_SYNTH, AID_K_MATCH = range(6)
-AID_K_COUNT = 12
+AID_K_RESAMPLE_SPEEDS, AID_K_SPEED_SELECT = 12, 13
+AID_K_COUNT = 14
 KERNEL_NAMES = ["stft_power", "peak_pick", "landmark_count", "landmark_write", "synth", "match", "resample",
-                "dedup", "index_build", "vote_hist", "hot_scan", "vote_final"]
+                "dedup", "index_build", "vote_hist", "hot_scan", "vote_final", "resample_speeds", "speed_select"]
 
 
 class EngineUnavailable(RuntimeError):
@@ -156,6 +157,10 @@ SIGNATURES = [
     ("aid_query_pcm_submit", ctypes.c_int, [P, P, P, I32, I32, P, P]),
     ("aid_exact_lane", ctypes.c_int, [P, P, P, I32, I32, I32, P, P, P]),
     ("aid_exact_windows", ctypes.c_int, [I64, I32, P, P, P]),
+    ("aid_speed_plan", ctypes.c_int, [I32, I32, I32, P, P, P, P]),
+    ("aid_speed_len", I64, [I64, I32, I32, I32]),
+    ("aid_resample_speeds", ctypes.c_int, [P, P, P, I32, I32, I32, P, I32, P, I64, P, P]),
+    ("aid_exact_lane_speeds", ctypes.c_int, [P, P, P, I32, I32, I32, I32, P, I32, I32, P, P, P, P]),
     ("aid_downmix", ctypes.c_int, [P, P, I64, P, P]),
     ("aid_resample_len", I64, [I64, I32, I32]),
     ("aid_resample", ctypes.c_int, [P, P, I64, I32, I32, I32, P, I64, P, P]),
@@ -188,6 +193,10 @@ SIGNATURES = [
 SIGNATURES += [(name + "_s16", res, args) for name, res, args in SIGNATURES
                if name in ("aid_extract", "aid_query_pcm", "aid_query_pcm_submit", "aid_query_windows",
                            "aid_query_windows_submit", "aid_exact_lane", "aid_resample", "aid_resample_batch_split")]
+# the int16 forms of the speed entry points are named after the s16 sibling they extend (aid_resample_s16,
+# aid_exact_lane_s16): aid_resample_s16_speeds, aid_exact_lane_s16_speeds
+SIGNATURES += [(name[:-len("_speeds")] + "_s16_speeds", res, args) for name, res, args in SIGNATURES
+               if name in ("aid_resample_speeds", "aid_exact_lane_speeds")]
 PCM_FORMATS = ("f32", "s16")
 
 _lib = None

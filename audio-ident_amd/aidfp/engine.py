@@ -302,7 +302,8 @@ class Engine:
              "k2_strips_x100": L.AID_FORCE_K2_STRIPS_X100, "k4_build": L.AID_FORCE_K4_BUILD,
              "exchange_fail": L.AID_FORCE_EXCHANGE_FAIL, "lane_gather": L.AID_FORCE_LANE_GATHER,
              "plane_rows": L.AID_FORCE_PLANE_ROWS, "k2_width": L.AID_FORCE_K2_WIDTH,
-             "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK}
+             "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK,
+             "speed_group": L.AID_FORCE_SPEED_GROUP}
 
     def force(self, what: str, value: int) -> None:
         """Test hook (aid_engine_force): pin one of the engine's own code paths, e.g. force("k5_path", 2)."""
@@ -317,8 +318,12 @@ class Engine:
 
     # -- extraction --
     def _fn(self, name: str, fmt: str):
-        """The C entry point `name` of a PCM format ("f32": itself, "s16": its _s16 twin)."""
-        return getattr(self._lib, name + _fmt_suffix(fmt))
+        """The C entry point `name` of a PCM format ("f32": itself, "s16": its _s16 twin; the speed entry points'
+        int16 forms carry the infix: aid_resample_s16_speeds)."""
+        sfx = _fmt_suffix(fmt)
+        if sfx and name.endswith("_speeds"):  # aid_resample_s16_speeds, aid_exact_lane_s16_speeds
+            return getattr(self._lib, name[:-len("_speeds")] + sfx + "_speeds")
+        return getattr(self._lib, name + sfx)
 
     def extract_host(self, clips: Sequence[np.ndarray], fmt: str = "f32") -> list[np.ndarray]:
         """Fingerprint host clips; returns one uint64 record array (hash | t1 << 32) per clip. fmt="s16": the clips
@@ -744,6 +749,64 @@ class Engine:
         check(fn(self._h, src, _p(offsets), n, loc, max_out, _p(out), _p(nout), None))
         # per-clip views of the one result array (4096 per-clip copies took ~3.5 ms of host time per lane call)
         return [r[:k] for r, k in zip(out.reshape(n, max_out), nout.tolist())]
+
+    # -- speed-tolerant exact lane (FPSPEC 8.2, 7.1) --
+    def speed_plan(self, sr_in: int, speed_pm: int):
+        """(up, down, hl, J) of speed `speed_pm` (per mille) for clips captured at sr_in (aid_speed_plan)."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        if not self._lib.aid_speed_plan(int(sr_in), self.sample_rate, int(speed_pm), *[ctypes.byref(x) for x in v]):
+            raise ValueError("bad sample rates or speed")
+        return tuple(x.value for x in v)
+
+    def speed_len(self, n: int, sr_in: int, speed_pm: int) -> int:
+        return int(self._lib.aid_speed_len(int(n), int(sr_in), self.sample_rate, int(speed_pm)))
+
+    def resample_speeds(self, src_ptr: int, offsets, channels: int, sr_in: int, speeds_pm, dst_ptr: int, cap: int,
+                        stream: int | None = None, fmt: str = "f32") -> np.ndarray:
+        """Every speed variant of every clip in one launch (aid_resample_speeds). Device PCM: clip c = frames
+        [offsets[c], offsets[c + 1]) of `channels` at sr_in. Returns the packed destination offsets, int64
+        [n_clips * n_speeds + 1]: pair (clip c, speed v) is dst[off[c * n_speeds + v] : off[c * n_speeds + v + 1]].
+        Asynchronous on `stream`."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        pm = np.ascontiguousarray(speeds_pm, dtype=np.int32)
+        n = len(offsets) - 1
+        dst_off = np.zeros(max(n, 0) * len(pm) + 1, dtype=np.int64)
+        check(self._fn("aid_resample_speeds", fmt)(self._h, ctypes.c_void_p(src_ptr), _p(offsets), n, int(channels),
+                                                   int(sr_in), _p(pm), len(pm), ctypes.c_void_p(dst_ptr), int(cap),
+                                                   _p(dst_off), ctypes.c_void_p(stream) if stream else None))
+        return dst_off
+
+    def exact_lane_speeds(self, clips: Sequence[np.ndarray] | None = None, sr_in: int = 0, channels: int = 1,
+                          speeds_pm=(0,), max_out: int = 0, *, pcm_ptr: int = 0, offsets: np.ndarray | None = None,
+                          fmt: str = "f32") -> tuple[list[np.ndarray], list[int]]:
+        """The exact lane over every speed variant of every clip, and per clip the best speed
+        (aid_exact_lane_speeds). Host clips ([n] mono or [n, 2] / interleaved stereo at sr_in), or device PCM
+        (pcm_ptr) with host offsets in frames. Returns (rows_per_clip, speed_pm_per_clip): the winner's rows as
+        exact_lane returns them, and its speed in per mille (0 for a clip without rows)."""
+        max_out = int(max_out) or 3 * self.max_results
+        sr_in = int(sr_in) or self.sample_rate
+        pm = np.ascontiguousarray(speeds_pm, dtype=np.int32)
+        if clips is not None:
+            arrs = _host_clips(clips, fmt)
+            if any(len(a) % channels for a in arrs):
+                raise ValueError("a stereo clip holds whole frames")
+            offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
+            if arrs:
+                offsets[1:] = np.cumsum([len(a) // channels for a in arrs])
+            pcm = _host_concat(arrs, int(offsets[-1]) * channels, dtype=arrs[0].dtype if arrs else np.float32)
+            src, loc = _p(pcm), AID_PCM_HOST
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            src, loc = ctypes.c_void_p(pcm_ptr), AID_PCM_DEVICE
+        n = len(offsets) - 1
+        if n <= 0:
+            return [], []
+        out = np.zeros(n * max_out, dtype=self.EXACT_DTYPE)
+        nout = np.zeros(n, dtype=np.int32)
+        speed = np.zeros(n, dtype=np.int32)
+        check(self._fn("aid_exact_lane_speeds", fmt)(self._h, src, _p(offsets), n, loc, int(channels), sr_in, _p(pm),
+                                                     len(pm), max_out, _p(out), _p(nout), _p(speed), None))
+        return [r[:k] for r, k in zip(out.reshape(n, max_out), nout.tolist())], speed.tolist()
 
     def downmix(self, stereo_ptr: int, n_frames: int, mono_ptr: int, stream: int | None = None) -> None:
         check(self._lib.aid_downmix(self._h, ctypes.c_void_p(stereo_ptr), int(n_frames), ctypes.c_void_p(mono_ptr),

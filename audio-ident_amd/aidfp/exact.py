@@ -44,6 +44,7 @@ class ScoredCandidate:
     aligned_hashes: int
     offset_seconds: float | None
     confidence: float = 0.0
+    speed_pm: int = 0  # the clip's chosen speed in per mille (speed search; 0 = nominal)
 
 
 @dataclass
@@ -54,6 +55,7 @@ class ExactMatch:
     confidence: float
     offset_seconds: float | None
     aligned_hashes: int
+    speed_pm: int = 0  # not in the reference: the clip's chosen speed in per mille (speed search; 0 = nominal)
 
 
 def pcm_duration_sec(pcm: bytes, sample_rate: int = SAMPLE_RATE) -> float:
@@ -169,7 +171,7 @@ async def enrich(top: list[ScoredCandidate], lookup: LookupFn) -> list[ExactMatc
         if meta is None:
             logger.warning("track %s not in metadata store, dropped", c.track_uuid)
             continue
-        out.append(ExactMatch(meta, c.confidence, c.offset_seconds, c.aligned_hashes))
+        out.append(ExactMatch(meta, c.confidence, c.offset_seconds, c.aligned_hashes, c.speed_pm))
     return out
 
 
@@ -191,6 +193,51 @@ async def run_exact_lane(pcm_16k: bytes, max_results: int = 10, *, query: QueryF
     return await enrich(rank(scored, max_results), lookup or _default_lookup)
 
 
+SPEED_MIN_PM, SPEED_MAX_PM = -500, 1000  # spec/FPSPEC.md 8.2
+
+
+def speed_grid(lo_pm: int = -40, hi_pm: int = 40, step_pm: int = 2) -> tuple[int, ...]:
+    """The speeds (per mille) of a search over [lo_pm, hi_pm], 0 included when it lies inside. The default step of
+    2 leaves a residual of at most 1 per mille between a true speed and the nearest grid point, at which a 5 s clip
+    still scored 16-68 distinct anchor frames against min_match 10 (300 queries, profiles/speed_residual_cpu.txt);
+    at a residual of 2 it scored 6-35 (95 % at or above 10), at 4 it scored 1-20. The default grid has 41 speeds."""
+    lo_pm, hi_pm, step_pm = int(lo_pm), int(hi_pm), int(step_pm)
+    if step_pm <= 0 or lo_pm > hi_pm or lo_pm < SPEED_MIN_PM or hi_pm > SPEED_MAX_PM:
+        raise ValueError("speed_grid: need step > 0 and -500 <= lo <= hi <= 1000")
+    # anchored at 0 when the range spans it, so the nominal speed is always a grid point
+    first = -((-lo_pm) // step_pm) * step_pm if lo_pm <= 0 <= hi_pm else lo_pm
+    return tuple(range(first, hi_pm + 1, step_pm))
+
+
+def _aligned(row) -> int:
+    try:
+        return int(row["aligned_hashes"])  # an engine row (numpy structured)
+    except (TypeError, IndexError, KeyError):
+        return int(row.aligned_hashes)  # ExactMatch / ScoredCandidate
+
+
+def select_speed(rows_per_variant: Sequence[Sequence], speeds_pm: Sequence[int], max_out: int | None = None):
+    """Speed selection of one clip (spec/FPSPEC.md 7.1), the host mirror of the engine's K8c. rows_per_variant[v]:
+    the exact lane's ranked rows of the clip's variant at speeds_pm[v] (engine rows, ExactMatch or ScoredCandidate
+    lists). A variant's key is the largest aligned_hashes among its first max_out rows (0 without rows); the winner
+    has the largest key, then the smaller |pm|, then the smaller pm, then the lower position. Returns (the winner's
+    rows cut to max_out, its speed), or ([], 0) when every key is 0."""
+    if len(rows_per_variant) != len(speeds_pm):
+        raise ValueError("select_speed: one row list per speed")
+    best, best_rank = None, None
+    for v, (rows, pm) in enumerate(zip(rows_per_variant, speeds_pm)):
+        rows = rows if max_out is None else rows[:max_out]
+        key = max((_aligned(r) for r in rows), default=0)
+        if key <= 0:
+            continue
+        rank_ = (-key, abs(int(pm)), int(pm), v)
+        if best_rank is None or rank_ < best_rank:
+            best, best_rank = rows, rank_
+    if best is None:
+        return [], 0
+    return best, best_rank[2]
+
+
 def candidates_from_rows(rows, names: dict[int, str], max_results: int) -> list[ScoredCandidate]:
     """Engine exact-lane rows (rank order) -> ScoredCandidate list: rows of tracks without a name
     (not in the service's map) are dropped before the top-N cut, as the per-window path drops
@@ -208,12 +255,14 @@ def candidates_from_rows(rows, names: dict[int, str], max_results: int) -> list[
 
 
 async def run_exact_lane_batch(clips: Sequence[bytes], max_results: int = 10, *, service=None,
-                               lookup: LookupFn | None = None) -> list[list[ExactMatch]]:
+                               lookup: LookupFn | None = None, speed_search: str | None = None,
+                               speeds_pm: Sequence[int] | None = None) -> list[list[ExactMatch]]:
     """run_exact_lane for a batch of 16 kHz f32le clips in one engine call (aid_exact_lane):
     sub-window fan-out, K1-K5 and the consensus/threshold/ranking kernel on the GPU; only the
     metadata lookup runs here. An engine failure, including an engine that cannot start
     (OlafError), gives [] for every clip: the reference logs a failed olaf query and carries on
-    (exact.py:163-171 sub-windows, :186-190 full clip)."""
+    (exact.py:163-171 sub-windows, :186-190 full clip). speed_search / speeds_pm: the speed-tolerant lane, as
+    FingerprintService.exact_batch takes them (every ExactMatch then carries the clip's speed_pm)."""
     import asyncio
 
     from .fingerprint import get_service
@@ -222,7 +271,11 @@ async def run_exact_lane_batch(clips: Sequence[bytes], max_results: int = 10, *,
         return []
     try:
         svc = service or get_service()
-        ranked = await asyncio.get_running_loop().run_in_executor(None, svc.exact_batch, list(clips), max_results)
+        if speed_search is None and speeds_pm is None:
+            call = (svc.exact_batch, list(clips), max_results)
+        else:
+            call = (svc.exact_batch, list(clips), max_results, speed_search, speeds_pm)
+        ranked = await asyncio.get_running_loop().run_in_executor(None, *call)
     except OlafError:
         logger.exception("exact lane: fingerprint engine unavailable")
         ranked = [[] for _ in clips]

@@ -443,21 +443,52 @@ class FingerprintService:
         self._rw.release_read()
         return _Answered(out)
 
-    def exact_batch(self, clips: list[bytes], max_results: int) -> list[list]:
-        """Batched exact lane over the engine (aid_exact_lane); ranked ScoredCandidate lists."""
-        from ._lib import EngineError
-        from .exact import candidates_from_rows
+    def exact_batch(self, clips: list[bytes], max_results: int, speed_search: str | None = None,
+                    speeds_pm=None) -> list[list]:
+        """Batched exact lane over the engine (aid_exact_lane); ranked ScoredCandidate lists.
 
+        speed_search (default: env AIDFP_SPEED_SEARCH, else off) adds the speed-tolerant lane (spec/FPSPEC.md 8.2,
+        7.1) for clips played fast or slow: "always" runs every clip through aid_exact_lane_speeds over speeds_pm
+        (default exact.speed_grid(): -40 .. +40 per mille in steps of 2); "fallback" runs the nominal lane first and
+        sends only the clips whose best aligned_hashes is below STRONG_MATCH_HASHES to the speed lane, whose answer
+        replaces the nominal one only if its key is strictly larger. Every candidate carries the clip's chosen speed
+        (speed_pm, 0 = nominal). None: the nominal lane alone, as ever."""
+        from ._lib import EngineError
+        from .exact import STRONG_MATCH_HASHES, candidates_from_rows, speed_grid
+
+        mode = speed_search if speed_search is not None else (os.environ.get("AIDFP_SPEED_SEARCH") or None)
+        if mode in ("", "off", "none"):
+            mode = None
+        if mode not in (None, "always", "fallback"):
+            raise ValueError(f'speed_search must be None, "always" or "fallback", not {mode!r}')
         with self._rw.read():
             eng = self._eng()
             pcms = [self._clip(c) for c in clips]
+            speeds = [0] * len(pcms)
             try:
-                rows = eng.exact_lane(pcms, **self._fmt_kw)
+                if mode == "always":
+                    grid = tuple(speeds_pm) if speeds_pm is not None else speed_grid()
+                    rows, speeds = eng.exact_lane_speeds(pcms, eng.sample_rate, 1, grid, **self._fmt_kw)
+                else:
+                    rows = eng.exact_lane(pcms, **self._fmt_kw)
+                if mode == "fallback":
+                    grid = tuple(speeds_pm) if speeds_pm is not None else speed_grid()
+                    key = [int(r["aligned_hashes"].max()) if len(r) else 0 for r in rows]
+                    weak = [i for i, (k, p) in enumerate(zip(key, pcms)) if k < STRONG_MATCH_HASHES and len(p)]
+                    if weak:
+                        srows, spm = eng.exact_lane_speeds([pcms[i] for i in weak], eng.sample_rate, 1, grid,
+                                                           **self._fmt_kw)
+                        for i, r, pm in zip(weak, srows, spm):
+                            if len(r) and int(r["aligned_hashes"].max()) > key[i]:
+                                rows[i], speeds[i] = r, pm
             except EngineError as exc:
                 logger.error("aidfp exact lane failed: %s", exc)
                 return [[] for _ in clips]
-            return [candidates_from_rows(r, self._names, max_results) if len(p) else []
-                    for r, p in zip(rows, pcms)]
+            out = [candidates_from_rows(r, self._names, max_results) if len(p) else [] for r, p in zip(rows, pcms)]
+            for cands, pm in zip(out, speeds):
+                for c in cands:
+                    c.speed_pm = int(pm)
+            return out
 
     def delete_track(self, name: str) -> bool:
         from ._lib import EngineError

@@ -22,7 +22,7 @@ ARCH = "gfx950"
 
 SOURCES = ["stft.hip", "peaks.hip", "landmarks.hip", "synth.hip", "index.hip", "index_sort.hip", "stream.hip",
            "resample.hip", "dedup.hip", "exact.hip", "vector.hip", "engine.cpp", "extract.cpp",
-           "index_host.cpp", "index_exchange.cpp", "query.cpp"]
+           "index_host.cpp", "index_exchange.cpp", "query.cpp", "speed.cpp"]
 FLAGS = [
     f"--offload-arch={ARCH}",
     "-O3",

@@ -25,6 +25,10 @@ void launch_resample(const void *src, bool s16, int64_t in_base, int64_t n, int 
                      int J, const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s,
                      int n_streams = 1, int64_t src_stride = 0, int64_t dst_stride = 0, const void *hist = nullptr,
                      int64_t hist_n = 0, int64_t hist_stride = 0);
+struct SpeedVarDev;  // aidfp_speed_plan.h
+void launch_resample_speeds(const void *src, bool s16, int channels, const int64_t *clip_off, const SpeedVarDev *vars,
+                            int n_speeds, const int64_t *blk_first, const int64_t *dst_off, int pair0, int n_pairs,
+                            int64_t blocks, int64_t lds_floats, float *dst, hipStream_t s);
 void launch_s16_to_f32(const int16_t *src, int64_t n, float *dst, hipStream_t s);
 int dedup_chunks(int64_t n_cat);
 void launch_dedup_scan(const uint32_t *cw, const int64_t *coff, const double *cdur, int64_t n_cat, const uint32_t *qw,
@@ -71,5 +75,7 @@ void launch_downmix(const float *in, int64_t n, float *out, hipStream_t s);
 void launch_window_gather(const void *src, bool s16, const int64_t *win, int n_win, int64_t max_len, float *dst, hipStream_t s);
 void launch_exact_consensus(const int32_t *rows, const int32_t *nrows, int mr, const int32_t *clip_win, int n_clips,
                             double sec, int max_out, void *out, int32_t *n_out, hipStream_t s);
+void launch_speed_select(const void *rows, const int32_t *nrows, int max_out, const int32_t *speeds_pm, int n_speeds,
+                         int n_clips, void *out, int32_t *n_out, int32_t *speed_out, hipStream_t s);
 void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
 }  // namespace aid

@@ -205,6 +205,10 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
                 return fail(AID_ERR_INVALID, "VEC_CHUNK: 0 default, else a multiple of 32 in [32, 4096]");
             e->vec.force_chunk = value;
             return AID_OK;
+        case AID_FORCE_SPEED_GROUP:
+            if (value < 0) return fail(AID_ERR_INVALID, "SPEED_GROUP must be >= 0");
+            e->speed_group = value;
+            return AID_OK;
         default:
             return fail(AID_ERR_INVALID, "aid_engine_force: unknown path id");
     }
@@ -280,8 +284,11 @@ int64_t aid_resample_len(int64_t n, int32_t sr_in, int32_t sr_out) {
     return (n * p.up + p.down - 1) / p.down;
 }
 
-// impulse: the unit impulse at the filter's centre instead of the designed taps (cached under -down)
-static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse, float **out) {
+}  // extern "C"
+
+// impulse: the unit impulse at the filter's centre instead of the designed taps (cached under -down); shared with
+// speed.cpp (engine_internal.h)
+int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse, float **out) {
     const std::pair<int32_t, int32_t> key{p.up, impulse ? -p.down : p.down};
     auto it = e->rs_taps.find(key);
     if (it != e->rs_taps.end()) {
@@ -301,6 +308,8 @@ static int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse,
     e->rs_taps[key] = std::move(taps);
     return AID_OK;
 }
+
+extern "C" {
 
 int aid_resample_range(aid_engine *e, const float *src, int64_t in_base, int64_t n, int32_t channels, int32_t sr_in,
                        int32_t sr_out, int64_t m_first, int64_t count, float *dst, void *stream) {

@@ -3,7 +3,8 @@
 // across their boundaries. engine.cpp: the engine itself, synth, resampling, dedup, the vector lane's wrappers,
 // profiling. extract.cpp: extraction and its results (aidfp_extract.h). index_host.cpp: the hash index
 // (aidfp_index.h). index_exchange.cpp: aid_comm and the index exchange (the only file that includes RCCL).
-// query.cpp: K5, the query entry points, the exact lane. Nothing here is part of the C ABI.
+// query.cpp: K5, the query entry points, the exact lane. speed.cpp: the speed fan-out and the speed lane
+// (aidfp_speed_plan.h). Nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "aidfp_index.h"
 #include "aidfp_launch.h"
 #include "aidfp_layout.h"
+#include "aidfp_speed_plan.h"
 #include "aidfp_vector.h"
 
 #pragma GCC visibility push(hidden)  // shared between the host files, not exported
@@ -110,6 +112,18 @@ struct aid_engine {
     DevBuf<int32_t> x_order, x_clipwin, x_nout;
     DevBuf<double> x_out;  // aid_exact_row, 3 x 8 bytes each
     std::map<std::pair<int32_t, int32_t>, DevBuf<float>> rs_taps;  // (up, down) -> device [up][J] taps
+    // speed fan-out (speed.cpp; FPSPEC 8.2, 7.1): the call's plan, its device tables ([clip_off | dst_off | blk_first]
+    // int64, the speeds' SpeedVarDev rows, the speeds), staged host PCM, a clip group's variant PCM, the winners
+    SpeedPlan sp_plan;
+    HostBuf<int64_t> sp_hidx;
+    HostBuf<uint8_t> sp_hvar;
+    DevBuf<int64_t> sp_idx;
+    DevBuf<uint8_t> sp_var;
+    DevBuf<int32_t> sp_seln;  // the winners' row counts [n_clips], then their speeds [n_clips]
+    DevBuf<float> sp_in, sp_pcm;
+    DevBuf<double> sp_sel;  // aid_exact_row, 3 x 8 bytes each
+    Event sp_ev;            // the last K6s launch: its tables and staging are free again behind it
+    int64_t speed_group = 0;  // aid_engine_force SPEED_GROUP: variant samples per clip group (0 = 1 GiB of them)
     // Chromaprint dedup catalog (insertion order) + scan scratch
     DevBuf<uint32_t> dd_words;
     DevBuf<int64_t> dd_off;
@@ -275,5 +289,11 @@ struct EngineCall {
 // extract.cpp; engine lock held
 int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
                    void *stream, const int64_t *ends = nullptr);
+// query.cpp; engine lock held: the exact lane up to K8b, rows and counts left in e->x_out / e->x_nout
+int exact_lane_device(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                      int32_t max_out, void *stream);
+// engine.cpp; engine lock held: the device [up][J] tap table of a plan from the engine's cache (impulse: the unit
+// impulse at the filter's centre, cached under -down)
+int resample_taps_dev(aid_engine *e, const ResamplePlan &p, bool impulse, float **out);
 
 #pragma GCC visibility pop

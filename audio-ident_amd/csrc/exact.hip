@@ -21,7 +21,8 @@
 // the per-window path on synthesised audio); tests/test_gpu_consensus_edges.py (K8b's decision edges on the
 // constructed index of tests/consensus_fixtures.py against the all-oracle lane: 7 / 8 aligned hashes, halving,
 // medians, confidence ties cut by max_out, kExactMaxRows staged rows; the builder's own preconditions:
-// tests/test_consensus_fixtures_host.py).
+// tests/test_consensus_fixtures_host.py); tests/test_gpu_speed_lane.py (K8c `speed_select` behind the speed lane,
+// against aidfp.exact.select_speed over the all-oracle lane; the rule itself: tests/test_speed_select_host.py).
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
 
@@ -169,6 +170,60 @@ __global__ __launch_bounds__(256) void k_rows_scatter(const int32_t *__restrict_
         const int q = order[i];
         for (int k = threadIdx.x; k < mr * 5; k += blockDim.x) dst[(size_t)q * mr * 5 + k] = src[(size_t)i * mr * 5 + k];
     }
+}
+
+// K8c `speed_select` (FPSPEC 7.1): one wave per clip over the K8b rows of its n_speeds variants (pair = clip *
+// n_speeds + v; rows [pair][max_out], counts [pair], where K8b left them). The key of a variant is the largest
+// aligned_hashes among its rows; the winner has the largest key, then the smaller |pm|, then the smaller pm, then the
+// lower position. Its rows go unchanged to out[clip][..]; a clip whose every key is 0 gets no rows and speed 0.
+constexpr int kSpeedMaxVariants = 256;  // == aidfp_speed_plan.h (n_speeds is checked there)
+
+__global__ __launch_bounds__(64) void k_speed_select(const ExactRow *__restrict__ rows, const int32_t *__restrict__ nrows,
+                                                     int max_out, const int32_t *__restrict__ speeds_pm, int n_speeds,
+                                                     ExactRow *__restrict__ out, int32_t *__restrict__ n_out,
+                                                     int32_t *__restrict__ speed_out) {
+    __shared__ int32_t s_key[kSpeedMaxVariants];
+    __shared__ int s_best;
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const size_t pair0 = (size_t)c * n_speeds;
+    for (int v = lane; v < n_speeds && v < kSpeedMaxVariants; v += 64) {
+        const int k = min(max(nrows[pair0 + v], 0), max_out);
+        int32_t key = 0;
+        for (int i = 0; i < k; ++i) key = max(key, rows[(pair0 + v) * max_out + i].aligned_hashes);
+        s_key[v] = key;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int best = -1;
+        for (int v = 0; v < n_speeds && v < kSpeedMaxVariants; ++v) {
+            const int32_t key = s_key[v];
+            if (key <= 0) continue;
+            bool better = best < 0;
+            if (!better) {
+                const int32_t bk = s_key[best], pm = speeds_pm[v], bp = speeds_pm[best];
+                better = key > bk || (key == bk && (abs(pm) < abs(bp) || (abs(pm) == abs(bp) && pm < bp)));
+            }
+            if (better) best = v;
+        }
+        s_best = best;
+        n_out[c] = best < 0 ? 0 : min(max(nrows[pair0 + best], 0), max_out);
+        speed_out[c] = best < 0 ? 0 : speeds_pm[best];
+    }
+    __syncthreads();
+    const int best = s_best;
+    if (best < 0) return;
+    const int k = min(max(nrows[pair0 + best], 0), max_out);
+    // a row is three 8-byte words
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(rows + (pair0 + best) * max_out);
+    uint64_t *dst = reinterpret_cast<uint64_t *>(out + (size_t)c * max_out);
+    for (int i = lane; i < 3 * k; i += 64) dst[i] = src[i];
+}
+
+void launch_speed_select(const void *rows, const int32_t *nrows, int max_out, const int32_t *speeds_pm, int n_speeds,
+                         int n_clips, void *out, int32_t *n_out, int32_t *speed_out, hipStream_t s) {
+    if (n_clips <= 0) return;
+    hipLaunchKernelGGL(k_speed_select, dim3((unsigned)n_clips), dim3(64), 0, s, reinterpret_cast<const ExactRow *>(rows),
+                       nrows, max_out, speeds_pm, n_speeds, reinterpret_cast<ExactRow *>(out), n_out, speed_out);
 }
 
 void launch_window_gather(const void *src, bool s16, const int64_t *win, int n_win, int64_t max_len, float *dst,

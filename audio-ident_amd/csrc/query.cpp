@@ -500,8 +500,11 @@ extern "C" int aid_exact_lane_s16(aid_engine *e, const int16_t *pcm, const int64
     return exact_lane_entry("aid_exact_lane_s16", e, pcm, kS16, offsets, n_clips, loc, max_out, out, n_out, stream);
 }
 
-static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
-                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
+// The lane up to K8b, engine lock held: the rows of clip c end in e->x_out[c * max_out ..] and their count in
+// e->x_nout[c], on the device, complete in stream order (exact_lane_locked copies them out; the speed lane, speed.cpp,
+// selects among them first)
+int exact_lane_device(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips, int32_t loc,
+                      int32_t max_out, void *stream) {
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_index(e)) return rc;
     hipStream_t s = pick_stream(e, stream);
@@ -580,6 +583,13 @@ static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const i
     launch_exact_consensus(e->q_rows.p, e->q_nrows.p, mr, e->x_clipwin.p, n_clips, sec, max_out, e->x_out.p, e->x_nout.p,
                            s);
     HIP_TRY(hipGetLastError());
+    return AID_OK;
+}
+
+static int exact_lane_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *offsets, int32_t n_clips,
+                             int32_t loc, int32_t max_out, aid_exact_row *out, int32_t *n_out, void *stream) {
+    if (int rc = exact_lane_device(e, pcm, fmt, offsets, n_clips, loc, max_out, stream)) return rc;
+    hipStream_t s = pick_stream(e, stream);
     HIP_TRY(hipMemcpyAsync(n_out, e->x_nout.p, (size_t)n_clips * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out, e->x_out.p, (size_t)n_clips * max_out * sizeof(aid_exact_row), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -10,6 +10,7 @@
 // minimum: input once (+ the J-sample window overlap per block) and output once.
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
+#include "aidfp_speed_plan.h"
 
 namespace aid {
 
@@ -401,6 +402,87 @@ void launch_s16_to_f32(const int16_t *src, int64_t n, float *dst, hipStream_t s)
     if (n <= 0) return;
     hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, s, src, n,
                        dst);
+}
+
+// K6s `resample_speeds` (FPSPEC 8.2): every (clip, speed, output block) of a clip group in ONE launch. A workgroup
+// finds its pair (clip * n_speeds + v) in the block-id prefix sums (uniform: scalar loads and a scalar search), reads
+// that speed's (up, down, hl, J, taps) from the device table, stages its input window once (stage_window: float or
+// s16, mono or stereo, the clip at any sample offset) and runs k_resample's fma chain, taps j = 0 .. J-1 in order, so
+// an output equals the single-pair kernels' bit for bit. Blocks are kSpeedBlock consecutive outputs of one pair, the
+// taps read from L1/L2 (the 41 tables of a 2 per mille grid are ~40 KB each; neighbouring workgroups share a speed).
+static_assert(kSpeedBlock == kResBlock, "K6s blocks are k_resample's");
+
+template <bool STEREO, typename T>
+__global__ __launch_bounds__(kResThreads) void k_resample_speeds(const T *__restrict__ src,
+                                                                 const int64_t *__restrict__ clip_off,
+                                                                 const SpeedVarDev *__restrict__ vars, int n_speeds,
+                                                                 const int64_t *__restrict__ blk_first,
+                                                                 const int64_t *__restrict__ dst_off, int pair0,
+                                                                 int n_pairs, float *__restrict__ dst) {
+    // pairs [pair0, pair0 + n_pairs) (whole clips); block blockIdx.x of them; dst[0] = the first output of pair0
+    extern __shared__ float sx[];
+    const int tid = threadIdx.x;
+    const int64_t b = blk_first[pair0] + blockIdx.x;
+    const int pair = pair0 + speed_find_pair(blk_first + pair0, n_pairs, b);
+    const int clip = pair / n_speeds;
+    const SpeedVarDev v = vars[pair - clip * n_speeds];
+    const T *x = src + clip_off[clip] * (STEREO ? 2 : 1);
+    const ResInT<T> in{x, 0, 0, 0, x, 0, clip_off[clip + 1] - clip_off[clip], 0};
+    const int64_t m_end = dst_off[pair + 1] - dst_off[pair];
+    float *__restrict__ out = dst + (dst_off[pair] - dst_off[pair0]);
+    const int up = v.up, down = v.down, hl = v.hl, J = v.J;
+    const int64_t m0 = (b - blk_first[pair]) * kResBlock;
+    const int64_t mlast = min(m0 + kResBlock - 1, m_end - 1);
+    const int64_t c0 = m0 * down + hl, q0 = c0 / up;
+    const int r0 = (int)(c0 - q0 * up);
+    const int64_t lo = q0 - (J - 1);
+    const int cnt = (int)((mlast * down + hl) / up - lo + 1);
+    stage_window<STEREO>(in, lo, cnt, sx, tid, kResThreads);
+    __syncthreads();
+    // output m0 + i: c = c0 + i * down; in 32 bits when r0 + 1023 * down fits (every rate pair but the extreme ones)
+    const bool small = (int64_t)kResBlock * down + up < 0x7FFFFFFF;
+#pragma unroll
+    for (int r = 0; r < kResPerThread; ++r) {
+        const int i = tid + r * kResThreads;
+        if (m0 + i >= m_end) break;
+        int p, q;  // phase, input index - q0
+        if (small) {
+            const uint32_t t = (uint32_t)r0 + (uint32_t)i * (uint32_t)down;
+            q = (int)(t / (uint32_t)up);
+            p = (int)(t - (uint32_t)q * (uint32_t)up);
+        } else {
+            const int64_t t = r0 + (int64_t)i * down;
+            q = (int)(t / up);
+            p = (int)(t - (int64_t)q * up);
+        }
+        const float *xp = sx + (q + J - 1);  // the input at c / up (window index c / up - lo)
+        float acc;
+        if (v.copy) {
+            acc = xp[-hl];  // up == down == 1: c = m + hl
+        } else {
+            acc = 0.0f;
+            const float *tp = v.taps + (int64_t)p * J;
+            for (int j = 0; j < J; ++j) acc = __builtin_fmaf(tp[j], xp[-j], acc);
+        }
+        out[m0 + i] = acc;
+    }
+}
+
+void launch_resample_speeds(const void *src, bool s16, int channels, const int64_t *clip_off, const SpeedVarDev *vars,
+                            int n_speeds, const int64_t *blk_first, const int64_t *dst_off, int pair0, int n_pairs,
+                            int64_t blocks, int64_t lds_floats, float *dst, hipStream_t s) {
+    if (blocks <= 0 || n_pairs <= 0) return;
+    const dim3 g((unsigned)blocks), b(kResThreads);
+    const size_t lds = (size_t)lds_floats * sizeof(float);
+#define AID_RS_SPEEDS(ST, T) \
+    hipLaunchKernelGGL((k_resample_speeds<ST, T>), g, b, lds, s, static_cast<const T *>(src), clip_off, vars, n_speeds, \
+                       blk_first, dst_off, pair0, n_pairs, dst)
+    if (s16) {
+        if (channels == 2) AID_RS_SPEEDS(true, int16_t); else AID_RS_SPEEDS(false, int16_t);
+    } else {
+        if (channels == 2) AID_RS_SPEEDS(true, float); else AID_RS_SPEEDS(false, float);
+    }
+#undef AID_RS_SPEEDS
 }
 
 }  // namespace aid

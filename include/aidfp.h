@@ -55,7 +55,9 @@ extern "C" {
 #define AID_K_VOTE_HIST 9    /* K5a: seen filter + global vote histogram (global match path) */
 #define AID_K_HOT_SCAN 10    /* K5h: histogram rows -> hot-bucket bitmaps */
 #define AID_K_VOTE_FINAL 11  /* K5b: exact (track, d) table of the hot votes, best d per track, rows */
-#define AID_K_COUNT 12       /* AID_K_MATCH (5) is the LDS match path (k_match_lds) */
+#define AID_K_RESAMPLE_SPEEDS 12 /* K6s: every speed variant of a clip group, one launch */
+#define AID_K_SPEED_SELECT 13    /* K8c: per-clip speed selection over the lane's rows */
+#define AID_K_COUNT 14       /* AID_K_MATCH (5) is the LDS match path (k_match_lds) */
 
 typedef struct aid_engine aid_engine;
 
@@ -117,6 +119,8 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
 #define AID_FORCE_VEC_PATH 10      /* K9 scan: 0 auto (MFMA), 1 MFMA, 2 VALU (explicit fmaf, one pair per lane) */
 #define AID_FORCE_VEC_CHUNK 11     /* 0 default, else a multiple of 32 in [32, 4096]: catalog rows per K9 scan workgroup
                                       and keys per selection slice (tests: a small catalog spans several chunks) */
+#define AID_FORCE_SPEED_GROUP 12   /* 0 default (2^28: 1 GiB), else variant samples per clip group of one
+                                      aid_exact_lane_speeds call (tests: a small call split into several groups) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
@@ -481,6 +485,46 @@ int aid_exact_lane_s16(aid_engine *e, const int16_t *pcm, const int64_t *offsets
    windows (3 for clips <= 5 s, mode 1; else 1 whole-clip window, mode 0) with sample bounds
    lo[w], len[w] (len 0 = no query, as the reference's empty piece, exact.py:150-160, :374-399). */
 int aid_exact_windows(int64_t n, int32_t sample_rate, int64_t *lo, int64_t *len, int32_t *mode);
+
+/* ---- speed-tolerant exact lane (spec/FPSPEC.md 8.2, 7.1) ----
+ * A recording played fast or slow (tempo and pitch together: radio, a turntable, a "sped-up" rip) shares almost no
+ * hash with its track. A speed is an integer pm in per mille, s = (1000 + pm) / 1000, pm in [-500, +1000]; the
+ * speed-pm variant of a clip captured at sr_in, for an engine at rate sr_e, is the FPSPEC 8 resampling of the clip
+ * for the rate pair (sr_in * 1000, sr_e * (1000 + pm)): what aid_resample returns for those two rates. Both factors
+ * must fit int32. */
+/* (up, down, hl, J) of a speed's rate pair; returns 0 on bad rates or speed, or a pair aid_resample rejects. No device. */
+int aid_speed_plan(int32_t sr_in, int32_t sr_out, int32_t speed_pm, int32_t *up, int32_t *down, int32_t *hl, int32_t *J);
+/* Samples of the variant of a clip of n frames (0 on bad input). No device. */
+int64_t aid_speed_len(int64_t n, int32_t sr_in, int32_t sr_out, int32_t speed_pm);
+/* Every speed variant of every clip in ONE launch (K6s). src: device, clip c = frames [offsets[c], offsets[c+1]) of
+   `channels` (HOST offsets, n_clips + 1); sr_out is the engine's rate. dst: device floats, capacity cap; the variant
+   of (clip c, speed v) lands at dst[dst_offsets[c * n_speeds + v] ..), packed in that order. dst_offsets: HOST
+   int64[n_clips * n_speeds + 1], written by the call (also when cap is too small: its last entry is the capacity
+   needed). Each variant equals aid_resample's output bit for bit. n_speeds in [1, 256]. Asynchronous on `stream`. */
+int aid_resample_speeds(aid_engine *e, const float *src, const int64_t *offsets, int32_t n_clips, int32_t channels,
+                        int32_t sr_in, const int32_t *speeds_pm, int32_t n_speeds, float *dst, int64_t cap,
+                        int64_t *dst_offsets, void *stream);
+/* int16 clips (FPSPEC 8.1), the rest the same. The int16 forms of the two speed entry points carry the infix of the
+   s16 call they extend (aid_resample_s16, aid_exact_lane_s16) */
+int aid_resample_s16_speeds(aid_engine *e, const int16_t *src, const int64_t *offsets, int32_t n_clips,
+                            int32_t channels, int32_t sr_in, const int32_t *speeds_pm, int32_t n_speeds, float *dst,
+                            int64_t cap, int64_t *dst_offsets, void *stream);
+/* aid_exact_lane over every speed variant of every clip, and per clip the best speed (FPSPEC 7.1). Clips as above
+   (frames of `channels` at sr_in; host PCM is staged by one copy, as in aid_extract). Each variant is a clip in its
+   own right at the engine's rate: its own aid_exact_windows plan, K1-K5 and the consensus. A variant's key is the
+   largest aligned_hashes among the rows the lane returns for it at max_out (0 without rows); the winner has the
+   largest key, then the smaller |pm|, then the smaller pm, then the lower position in speeds_pm. out: host
+   [n_clips][max_out], the winner's rows unchanged; n_out: host [n_clips]; speed_pm_out: host [n_clips], the winner's
+   speed (0 for a clip without rows). Variant PCM lives in an engine buffer, 1 GiB per clip group (whole clips);
+   only the winners' rows leave the device. Synchronous; safe to call from several threads, like aid_exact_lane. */
+int aid_exact_lane_speeds(aid_engine *e, const float *pcm, const int64_t *offsets, int32_t n_clips,
+                          int32_t pcm_location, int32_t channels, int32_t sr_in, const int32_t *speeds_pm,
+                          int32_t n_speeds, int32_t max_out, aid_exact_row *out, int32_t *n_out,
+                          int32_t *speed_pm_out, void *stream);
+int aid_exact_lane_s16_speeds(aid_engine *e, const int16_t *pcm, const int64_t *offsets, int32_t n_clips,
+                              int32_t pcm_location, int32_t channels, int32_t sr_in, const int32_t *speeds_pm,
+                              int32_t n_speeds, int32_t max_out, aid_exact_row *out, int32_t *n_out,
+                              int32_t *speed_pm_out, void *stream);
 
 /* Streaming front end (config 5): interleaved f32 stereo [n_frames][2] -> mono [n_frames] on the
    device, m = (L + R) * 0.5f (the ffmpeg -ac 1 role, decode.py:50-51). Device pointers, stereo
