@@ -184,6 +184,7 @@ SIGNATURES = [
     ("aid_vibe_lane", ctypes.c_int, [P, P, I32, I32, I32, I32, ctypes.c_double, P, ctypes.c_double, I32, P, P, P]),
     ("aid_vec_save", ctypes.c_int, [P, ctypes.c_char_p]),
     ("aid_vec_load", ctypes.c_int, [P, ctypes.c_char_p]),
+    ("aid_vec_stats", ctypes.c_int, [P, P, I32, I32]),
     ("aid_profile_enable", ctypes.c_int, [P, I32]),
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),

@@ -470,6 +470,14 @@ class Engine:
                          "lds_path_workgroups_per_cu", "fallback_heavy", "fallback_table", "fallback_distinct",
                          "fallback_tracks", "fallback_rows", "k2_width", "k2_strips"), (int(x) for x in out)))
 
+    def vec_stats(self, reset: bool = False) -> dict:
+        """Cumulative K9 counters (aid_vec_stats): the route of each query batch, the slice route's select launches, the
+        largest candidate count (a maximum), the catalog copies of a growth, and scan launches by path."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._lib.aid_vec_stats(self._h, _p(out), 8, 1 if reset else 0))
+        return dict(zip(("batches_threshold", "batches_ineligible", "batches_overflow", "slice_selects", "max_candidates",
+                         "grow_copies", "scans_mfma", "scans_valu"), (int(x) for x in out)))
+
     # ---- PCM front-end (FPSPEC 8): downmix + resample, device buffers ----
     def resample_len(self, n: int, sr_in: int, sr_out: int) -> int:
         return int(self._lib.aid_resample_len(int(n), int(sr_in), int(sr_out)))

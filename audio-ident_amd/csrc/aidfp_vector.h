@@ -20,6 +20,7 @@ constexpr int kVecScanChunk = 1024;     // default catalog rows per scan workgro
 constexpr int kVecMaxSlice = 1024;      // default entries per slice maximum of the threshold route
 constexpr int kVecCandCap = 4096;       // candidates per query of the threshold route (one sort in LDS)
 constexpr int kVecSelectSlice = 4096;   // default keys per selection workgroup (one bitonic sort in LDS)
+constexpr int kVecStats = 8;            // counters of aid_vec_stats
 
 // Stored layout of a [rows][dim] matrix (catalog and query tiles alike): rows in tiles of 32, and within a tile
 // the float at (row i, k) sits at ((k >> 3) * 2 + (k & 1)) * 128 + i * 4 + ((k & 7) >> 1). Lane (i, h) of a wave
@@ -43,6 +44,9 @@ struct VecCatalog {
     std::vector<uint8_t> h_dead;
     int force_path = 0;   // AID_FORCE_VEC_PATH
     int force_chunk = 0;  // AID_FORCE_VEC_CHUNK
+    // aid_vec_stats, in its order: batches by threshold, not eligible, overflowed; slice-route select launches;
+    // largest candidate count; reallocations that copied rows; MFMA and VALU scan launches
+    int64_t st[kVecStats] = {};
     // scratch
     DevBuf<float, 64> d_raw, d_q, d_scores;
     DevBuf<unsigned long long, 64> d_keys0, d_keys1, d_cand;

@@ -589,6 +589,15 @@ int aid_vec_save(aid_engine *e, const char *path) { VEC_CALL(e, nullptr, vec_sav
 
 int aid_vec_load(aid_engine *e, const char *path) { VEC_CALL(e, nullptr, vec_load(e->vec, path, s)); }
 
+int aid_vec_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
+    if (!e || (n > 0 && !out)) return fail(AID_ERR_INVALID, "aid_vec_stats: bad argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (int i = 0; i < n && i < kVecStats; ++i) out[i] = e->vec.st[i];
+    if (reset)
+        for (auto &v : e->vec.st) v = 0;
+    return AID_OK;
+}
+
 int aid_profile_enable(aid_engine *e, int32_t on) {
     if (!e) return fail(AID_ERR_INVALID, "null engine");
     e->profiling = on != 0;

@@ -457,6 +457,7 @@ static int vec_grow(VecCatalog &c, int64_t rows, hipStream_t s) {
         if (c.d_vecs.p) (void)hipDeviceSynchronize();
         std::swap(c.d_vecs, nb);  // nb frees the old block
         c.cap_rows = cap;
+        if (keep) ++c.st[5];
     }
     if ((size_t)rows > c.d_track.n) {  // payload columns: rebuilt from the host mirror
         const size_t cap = (size_t)c.cap_rows;
@@ -593,6 +594,7 @@ static int vec_scan_batch(VecCatalog &c, const float *dq, int nb, hipStream_t s)
     if (c.force_path == 2) {
         hipLaunchKernelGGL(k_vec_scan_valu, dim3((unsigned)((ns + 255) / 256), (unsigned)nb), dim3(256), 0, s, c.d_vecs.p, ns,
                            c.d_q.p, dim, c.d_scores.p);
+        ++c.st[7];
     } else {
         const int chunk = c.force_chunk ? c.force_chunk : kVecScanChunk;
         const int tiles_per_wg = std::max(1, chunk / 32);
@@ -603,6 +605,7 @@ static int vec_scan_batch(VecCatalog &c, const float *dq, int nb, hipStream_t s)
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_vec_scan_mfma<512>, dim3(gx, (unsigned)nqt), dim3(512), lds, s, c.d_vecs.p, n_tiles, tiles_per_wg,
                            c.d_q.p, dim, c.d_scores.p, ns);
+        ++c.st[6];
     }
     VEC_TRY(hipGetLastError());
     return AID_OK;
@@ -678,6 +681,8 @@ static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int locat
             VEC_TRY(hipMemcpyAsync(cnt, c.d_ccnt.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
             VEC_TRY(hipStreamSynchronize(s));
             const int most = *std::max_element(cnt, cnt + nb);
+            c.st[4] = std::max<int64_t>(c.st[4], most);
+            ++c.st[most <= kVecCandCap ? 0 : 2];
             if (most <= kVecCandCap) {  // every list fits: one sort each
                 const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
                 hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
@@ -687,6 +692,8 @@ static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int locat
                 in = c.d_keys0.p;
                 in_stride = keep;
             }
+        } else {
+            ++c.st[1];
         }
         if (!in) {
             int64_t n_in = c.n;
@@ -698,6 +705,7 @@ static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int locat
                                    first ? c.d_scores.p : nullptr, ns, c.d_dead.p, in, in_stride, n_in, slice, keep, out,
                                    out_stride);
                 VEC_TRY(hipGetLastError());
+                ++c.st[3];
                 in = out;
                 in_stride = out_stride;
                 n_in = out_stride;

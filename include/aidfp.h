@@ -379,6 +379,14 @@ int aid_vibe_lane(aid_engine *e, const float *queries, int32_t nq, int32_t locat
    AID_ERR_INVALID and leaves the catalog as it was. */
 int aid_vec_save(aid_engine *e, const char *path);
 int aid_vec_load(aid_engine *e, const char *path);
+/* Cumulative vector-lane counters since the last reset (the first n of 8), counted on the host. A batch is one scan +
+   selection pass of at most 64 queries of aid_vec_search / aid_vibe_lane: out[0] batches whose hit lists came from
+   the threshold route, [1] batches not eligible for it (fewer slices than `limit`, or more than 4096 of them),
+   [2] batches that tried it and overflowed a candidate list (answered slice by slice, like [1]), [3] k_vec_select
+   launches of the slice-by-slice route (one per pass), [4] the largest candidate count read back (a maximum, not a
+   sum; it may exceed 4096, which is what [2] counts), [5] catalog reallocations that copied stored rows, [6] MFMA
+   scan launches and [7] VALU scan launches (aid_vec_scores counts in these two as well). */
+int aid_vec_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
 
 /* ---- native multi-GPU exchange (SURVEY.md 8b "aid_allgather_index", 8e) ----
  * One process per GPU. Rank 0 calls aid_comm_id, the host hands the 128 id bytes to every

@@ -14,7 +14,7 @@ from aidfp import _lib
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "ref_vibe.json"
 NEW_SYMBOLS = ["aid_vec_reset", "aid_vec_add", "aid_vec_remove", "aid_vec_compact", "aid_vec_count", "aid_vec_search",
-               "aid_vec_scores", "aid_vec_aggregate", "aid_vibe_lane", "aid_vec_save", "aid_vec_load"]
+               "aid_vec_scores", "aid_vec_aggregate", "aid_vibe_lane", "aid_vec_save", "aid_vec_load", "aid_vec_stats"]
 
 
 @pytest.fixture(scope="module")
