@@ -28,6 +28,9 @@ AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK, AID_FORCE_SPEED_GROUP = 10, 11, 12
 AID_K_STFT, AID_K_PEAKS, AID_K_LANDMARK_COUNT, AID_K_LANDMARK_WRITE, AID_K_SYNTH, AID_K_MATCH = range(6)
 AID_K_RESAMPLE_SPEEDS, AID_K_SPEED_SELECT = 12, 13
 AID_K_COUNT = 14
+AID_MEL_FRAMES, AID_MEL_BANDS, AID_MEL_BINS, AID_MEL_WINDOW = 1001, 64, 513, 480000
+AID_MEL_ZERO, AID_MEL_REPEATPAD = 0, 1
+AID_MEL_BANK_SLANEY, AID_MEL_BANK_HTK, AID_MEL_BANK_CUSTOM = 0, 1, 2
 KERNEL_NAMES = ["stft_power", "peak_pick", "landmark_count", "landmark_write", "synth", "match", "resample",
                 "dedup", "index_build", "vote_hist", "hot_scan", "vote_final", "resample_speeds", "speed_select"]
 
@@ -96,6 +99,18 @@ class AidVibeRow(ctypes.Structure):
         ("final_score", ctypes.c_double),
         ("base_score", ctypes.c_double),
         ("diversity_bonus", ctypes.c_double),
+    ]
+
+
+class AidMelChunk(ctypes.Structure):
+    _fields_ = [
+        ("clip", ctypes.c_int32),
+        ("chunk_index", ctypes.c_int32),
+        ("start", ctypes.c_int64),
+        ("r", ctypes.c_int32),
+        ("rep", ctypes.c_int32),
+        ("offset_sec", ctypes.c_double),
+        ("duration_sec", ctypes.c_double),
     ]
 
 
@@ -185,6 +200,10 @@ SIGNATURES = [
     ("aid_vec_save", ctypes.c_int, [P, ctypes.c_char_p]),
     ("aid_vec_load", ctypes.c_int, [P, ctypes.c_char_p]),
     ("aid_vec_stats", ctypes.c_int, [P, P, I32, I32]),
+    ("aid_mel_configure", ctypes.c_int, [P, I32, ctypes.c_double, ctypes.c_double, P]),
+    ("aid_mel_filters", ctypes.c_int, [P, P]),
+    ("aid_mel_plan", ctypes.c_int, [P, I32, I32, I64, P, P, I64]),
+    ("aid_logmel", ctypes.c_int, [P, P, P, P, I32, I32, I32, I64, P, I64, I32, P, P, P]),
     ("aid_profile_enable", ctypes.c_int, [P, I32]),
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),
@@ -198,6 +217,8 @@ SIGNATURES += [(name + "_s16", res, args) for name, res, args in SIGNATURES
 # aid_exact_lane_s16): aid_resample_s16_speeds, aid_exact_lane_s16_speeds
 SIGNATURES += [(name[:-len("_speeds")] + "_s16_speeds", res, args) for name, res, args in SIGNATURES
                if name in ("aid_resample_speeds", "aid_exact_lane_speeds")]
+# K10's int16 form: aid_logmel_pcm16
+SIGNATURES += [(name + "_pcm16", res, args) for name, res, args in SIGNATURES if name == "aid_logmel"]
 PCM_FORMATS = ("f32", "s16")
 
 _lib = None

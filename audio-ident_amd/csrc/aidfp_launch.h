@@ -77,5 +77,9 @@ void launch_exact_consensus(const int32_t *rows, const int32_t *nrows, int mr, c
                             double sec, int max_out, void *out, int32_t *n_out, hipStream_t s);
 void launch_speed_select(const void *rows, const int32_t *nrows, int max_out, const int32_t *speeds_pm, int n_speeds,
                          int n_clips, void *out, int32_t *n_out, int32_t *speed_out, hipStream_t s);
+struct MelChunkDev;  // aidfp_mel.h
+struct MelTables;
+void launch_logmel(const void *pcm, bool s16, const MelChunkDev *chunks, int64_t chunk0, int64_t n, const MelTables *tab,
+                   const float *wc, float *out, hipStream_t s);
 void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
 }  // namespace aid

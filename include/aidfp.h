@@ -388,6 +388,59 @@ int aid_vec_load(aid_engine *e, const char *path);
    scan launches and [7] VALU scan launches (aid_vec_scores counts in these two as well). */
 int aid_vec_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
 
+/* ---- CLAP log-mel front end (spec/FPSPEC.md 10; K10, csrc/mel.hip) ----
+ * What the reference computes on the host before its CLAP model sees a sample: chunk_audio (10 s chunks, 5 s hop,
+ * app/audio/embedding.py:101-152) and ClapFeatureExtractor's [1001][64] log-mel image per chunk. The input is mono
+ * 48 kHz PCM (aid_resample gives it on the device), the output a [chunks][1001][64] float plane a device model
+ * reads in place. The model itself stays with the caller. */
+#define AID_MEL_FRAMES 1001
+#define AID_MEL_BANDS 64
+#define AID_MEL_BINS 513
+#define AID_MEL_WINDOW 480000
+#define AID_MEL_ZERO 0      /* ingest: chunk_audio's plan, a short last chunk is zero-filled */
+#define AID_MEL_REPEATPAD 1 /* query: one chunk per clip; shorter than 10 s: repeated floor(480000 / n) times, then
+                               zero-filled; longer: the 10 s from `start` on */
+#define AID_MEL_BANK_SLANEY 0 /* slaney scale and norm (the extractor's mel_filters_slaney: truncation != "fusion") */
+#define AID_MEL_BANK_HTK 1    /* htk scale, no norm (mel_filters: truncation == "fusion") */
+#define AID_MEL_BANK_CUSTOM 2 /* the caller's own table */
+
+/* one chunk of a plan: samples [start, start + r) of clip `clip`; rep = repetitions (1 in zero mode) */
+typedef struct aid_mel_chunk {
+    int32_t clip;
+    int32_t chunk_index;
+    int64_t start;
+    int32_t r;
+    int32_t rep;
+    double offset_sec;   /* start / 48000 */
+    double duration_sec; /* r / 48000 */
+} aid_mel_chunk;
+
+/* Chooses the filter bank; required once before aid_logmel. SLANEY / HTK: built on the host in binary64 from fmin and
+   fmax (Hz, 0 <= fmin < fmax <= 24000), rounded once; `filters` must be NULL. CUSTOM: `filters` is a host
+   [513][64] table (fmin, fmax ignored): every band's non-zero weights must be contiguous, non-negative and finite,
+   no band may be empty, none may weight bin 512. Synchronous. */
+int aid_mel_configure(aid_engine *e, int32_t bank, double fmin, double fmax, const float *filters);
+/* The configured table, host out[513][64]. */
+int aid_mel_filters(aid_engine *e, float *out);
+/* Host only, no engine: the chunk plan of n_clips clip lengths (samples). *n_chunks receives the chunk count;
+   meta_out (may be NULL) receives the first min(count, meta_cap) chunks. `start` matters in REPEATPAD mode for clips
+   longer than 480000 samples and must lie in [0, n - 480000] for each of them. */
+int aid_mel_plan(const int64_t *lengths, int32_t n_clips, int32_t mode, int64_t start, int64_t *n_chunks,
+                 aid_mel_chunk *meta_out, int64_t meta_cap);
+/* K10 over every chunk of the clips pcm[clip_off[c] .. clip_off[c] + clip_len[c]) (offsets in samples from `pcm`;
+   location AID_PCM_HOST or AID_PCM_DEVICE). out[chunk][1001][64] floats, in device memory (out_location
+   AID_PCM_DEVICE, the normal case: the call returns with the kernel queued on `stream`) or host memory (the call
+   waits). *n_chunks receives the chunk count, `meta` (host, may be NULL) one entry per chunk. More chunks than
+   out_cap_chunks: AID_ERR_INVALID with *n_chunks set and nothing written. No sample outside a clip is read. */
+int aid_logmel(aid_engine *e, const float *pcm, const int64_t *clip_off, const int64_t *clip_len, int32_t n_clips,
+               int32_t location, int32_t mode, int64_t start, float *out, int64_t out_cap_chunks, int32_t out_location,
+               aid_mel_chunk *meta, int64_t *n_chunks, void *stream);
+/* The same over int16 PCM (FPSPEC 8.1: x = q / 32768), offsets and lengths in int16 samples. */
+int aid_logmel_pcm16(aid_engine *e, const int16_t *pcm, const int64_t *clip_off, const int64_t *clip_len,
+                        int32_t n_clips, int32_t location, int32_t mode, int64_t start, float *out,
+                        int64_t out_cap_chunks, int32_t out_location, aid_mel_chunk *meta, int64_t *n_chunks,
+                        void *stream);
+
 /* ---- native multi-GPU exchange (SURVEY.md 8b "aid_allgather_index", 8e) ----
  * One process per GPU. Rank 0 calls aid_comm_id, the host hands the 128 id bytes to every
  * rank (any side channel: torch.distributed store, MPI, a file), then every rank calls
