@@ -20,7 +20,7 @@ void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, 
                       hipStream_t s);
 void launch_synth(float *out, const uint32_t *tracks, const int64_t *starts, int n_clips, int64_t n, int sr,
                   int noise_a, uint32_t salt, int fmax_hz, bool envelope, const int16_t *sin_tab, hipStream_t s);
-int64_t resample_lds_floats(int up, int down, int J);
+// (the launch shape and what is refused: aidfp_resample_plan.h)
 void launch_resample(const void *src, bool s16, int64_t in_base, int64_t n, int channels, int up, int down, int hl,
                      int J, const float *taps, float *dst, int64_t m_first, int64_t count, hipStream_t s,
                      int n_streams = 1, int64_t src_stride = 0, int64_t dst_stride = 0, const void *hist = nullptr,

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "aidfp_resample_plan.h"
 #include "engine_internal.h"
 #include "resample_design.h"
 
@@ -341,9 +342,8 @@ static int resample_batch(aid_engine *e, const void *src, PcmFmt fmt, int64_t sr
                                                  : "aid_resample: stereo src must be 8-byte aligned");
     if (channels == 1 && fmt == kS16 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(hist)) & 1))
         return fail(AID_ERR_INVALID, "aid_resample: s16 src must be 2-byte aligned");
-    if (resample_lds_floats(p.up, p.down, p.J) * 4 > 65536)
-        return fail(AID_ERR_INVALID, "aid_resample: down/up ratio too large (LDS window > 64 KB)");
-    if ((int64_t)p.up * p.J > (1 << 24)) return fail(AID_ERR_INVALID, "aid_resample: tap table too large");
+    if (const ResLaunch pl = resample_launch_plan(p.up, p.down, p.J); pl.path == kResReject)
+        return fail(AID_ERR_INVALID, std::string("aid_resample: ") + resample_status_text(pl.status));
     std::lock_guard<std::mutex> lk(e->mu);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = pick_stream(e, stream);

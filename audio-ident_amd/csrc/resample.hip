@@ -6,19 +6,16 @@
 // store instruction writes 1 KB contiguous). It stages the input window those outputs touch
 // ONCE into LDS, downmixed to mono at staging time (float2 loads for stereo), zero outside the
 // clip; every output then runs its J-tap dot product from LDS with the phase row of the
-// [up][J] tap table, itself staged in LDS when it fits 48 KB (else read from L1/L2). HBM traffic is the algorithmic
+// [up][J] tap table, read from L1/L2 (no rate pair that aid_resample accepts has a table small enough
+// to stage beside its window: tests/test_resample_plan_host.py scans them all). HBM traffic is the algorithmic
 // minimum: input once (+ the J-sample window overlap per block) and output once.
+// Which form a rate pair runs, and its launch shape, is decided in aidfp_resample_plan.h (host only).
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
+#include "aidfp_resample_plan.h"
 #include "aidfp_speed_plan.h"
 
 namespace aid {
-
-constexpr int kResThreads = 256;
-constexpr int kResPerThread = 4;
-constexpr int kResBlock = kResThreads * kResPerThread;
-
-constexpr int kResMaxLdsTaps = 12288;  // floats (48 KB): larger tables are read from L1/L2
 
 // The input of one launch: stream frames [b_base, b_base + b_n) at b + y * b_stride and, optionally, the frames
 // [a_base, a_base + a_n) just before them at a + y * a_stride (y = stream of a batch), so a live stream's chunk is read
@@ -155,7 +152,7 @@ __device__ __forceinline__ void stage_window(const ResInT<T> &in, int64_t lo, in
     }
 }
 
-// MODE 0: taps from L1/L2, 1: taps staged in LDS, 2: integer decimation (up == 1): one phase,
+// MODE 0: per-lane phase rows, taps from L1/L2; 2: integer decimation (up == 1): one phase,
 // the taps are wave-uniform and read as scalar loads (no LDS traffic for them)
 template <bool STEREO, int MODE, typename T = float>
 __global__ __launch_bounds__(kResThreads) void k_resample(ResInT<T> in, int up, int down, int hl, int J,
@@ -164,14 +161,9 @@ __global__ __launch_bounds__(kResThreads) void k_resample(ResInT<T> in, int up, 
     // Outputs m_first .. m_end-1 (stream indices) go to dst[m - m_first].
     // blockIdx.y = stream of a batch: its input as ResIn says, its output at dst + y * dst_stride (floats)
     dst += (int64_t)blockIdx.y * dst_stride;
-    extern __shared__ float smem[];
+    static_assert(MODE == 0 || MODE == 2, "k_resample: MODE 0 (rational) or 2 (integer decimation)");
+    extern __shared__ float sx[];  // the input window
     const int tid = threadIdx.x;
-    // [up][J] tap table first (when it fits), then the input window
-    constexpr bool LDS_TAPS = MODE == 1;
-    float *sx = LDS_TAPS ? smem + ((up * J + 3) & ~3) : smem;
-    if constexpr (LDS_TAPS) {
-        for (int i = tid; i < up * J; i += kResThreads) smem[i] = taps[i];
-    }
     const int64_t m0 = m_first + (int64_t)blockIdx.x * kResBlock;
     const int64_t mlast = min(m0 + kResBlock - 1, m_end - 1);
     const int64_t lo = (m0 * down + hl) / up - (J - 1);
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(kResThreads) void k_resample(ResInT<T> in, int up, 
             for (int j = 0; j < J; ++j) acc = __builtin_fmaf(taps[j], xp[-j], acc);  // taps[j]: uniform
         } else {
             const int p = (int)(c % up);
-            const float *tp = (LDS_TAPS ? smem : taps) + (int64_t)p * J;
+            const float *tp = taps + (int64_t)p * J;
             const float *xp = sx + (c / up - lo);
             for (int j = 0; j < J; ++j) acc = __builtin_fmaf(tp[j], xp[-j], acc);
         }
@@ -204,15 +196,7 @@ __global__ __launch_bounds__(kResThreads) void k_resample(ResInT<T> in, int up, 
 // instead of J single-dword reads (MODE 2). Same fma chain per output (taps j = 0..J-1 in order), so the outputs are
 // MODE 2's bit for bit. kDecR 4 (80 VGPRs, 6 waves per SIMD): 98 us per 256-stream push against MODE 2's 105 and
 // kDecR 8's 155 (164 VGPRs, 3 waves per SIMD; profiles/r06p_k6_decimate_ab.txt): K6 is not bound by its LDS reads.
-#ifndef AID_K6_DECR
-#define AID_K6_DECR 4
-#endif
-constexpr int kDecR = AID_K6_DECR;
-constexpr int kDecThreads = 256;
-
-template <int DOWN, int J>
-constexpr int dec_window() { return (kDecThreads * kDecR - 1) * DOWN + J; }
-
+// (kDecR and kDecThreads: aidfp_resample_plan.h)
 template <bool STEREO, int DOWN, int J, typename T = float>
 __global__ __launch_bounds__(kDecThreads) void k_decimate(ResInT<T> in, int hl, const float *__restrict__ taps,
                                                           float *__restrict__ dst, int64_t m_first, int64_t m_end,
@@ -221,7 +205,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decimate(ResInT<T> in, int hl, 
     constexpr int NX = (kDecR - 1) * DOWN + J;  // inputs of one thread's outputs
     constexpr int NX4 = (NX + 3) / 4;
     dst += (int64_t)blockIdx.y * dst_stride;
-    extern __shared__ float sx[];  // dec_window() + 4 floats (the last run's 16-B over-read)
+    extern __shared__ float sx[];  // dec_window(DOWN, J) + 4 floats (the last run's 16-B over-read)
     const int tid = threadIdx.x;
     const int64_t m0 = m_first + (int64_t)blockIdx.x * (kDecThreads * kDecR);
     const int64_t mlast = min(m0 + kDecThreads * kDecR - 1, m_end - 1);
@@ -268,8 +252,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decimate(ResInT<T> in, int hl, 
 // 8-tap chunk (L1-resident table) and runs kResR dot products with them. Per output that is
 // J input reads from LDS (+ J / kResR tap loads) instead of 2J LDS reads with per-lane phase
 // rows (which also bank-conflicted). Same fma chain per output (taps j = 0..J-1 in order).
-constexpr int kResR = 16;  // outputs per thread (one phase)
-
+// (kResR outputs per thread: aidfp_resample_plan.h)
 template <bool STEREO, typename T = float>
 __global__ __launch_bounds__(256) void k_resample_phase(ResInT<T> in, int up, int down, int hl, int J,
                                                        const float *__restrict__ taps, float *__restrict__ dst,
@@ -311,24 +294,6 @@ __global__ __launch_bounds__(256) void k_resample_phase(ResInT<T> in, int up, in
     }
 }
 
-// phase-major blocks hold up * kResR outputs: used while that window stays small (common rate
-// pairs: up = 147, 160, 441); very large up (near-coprime rates) keep the 1024-output blocks
-static bool use_phase(int up, int down, int J) {
-    return up > 1 && up <= 1024 && ((int64_t)up * kResR - 1) * down / up + J + 2 <= 12288;
-}
-
-static int64_t window_floats(int up, int down, int J) {
-    if (use_phase(up, down, J)) return ((int64_t)up * kResR - 1) * down / up + J + 2;
-    return (int64_t)(kResBlock - 1) * down / up + J + 2;
-}
-
-static bool taps_in_lds(int up, int J) { return up > 1 && (int64_t)up * J <= kResMaxLdsTaps; }
-
-int64_t resample_lds_floats(int up, int down, int J) {
-    if (use_phase(up, down, J)) return window_floats(up, down, J);
-    return window_floats(up, down, J) + (taps_in_lds(up, J) ? (((int64_t)up * J + 3) & ~3) : 0);
-}
-
 // n_streams > 1: the same output range of n_streams streams in one launch (grid.y = stream), each stream's input
 // src_stride samples (of T) after the previous one's and its output dst_stride floats after; bit for bit the outputs of
 // n_streams single launches (same staging, same fma chain per output). With hist_n > 0 the input is two parts:
@@ -339,41 +304,32 @@ static void launch_resample_t(const T *src, int64_t in_base, int64_t n, int chan
                               int64_t src_stride, int64_t dst_stride, const T *hist, int64_t hist_n, int64_t hist_stride) {
     if (count <= 0 || n_streams <= 0) return;
     const ResInT<T> in{hist_n > 0 ? hist : src, in_base - hist_n, hist_n, hist_stride, src, in_base, n, src_stride};
-    if (use_phase(up, down, J)) {
-        const int64_t per = (int64_t)up * kResR;
-        const dim3 g((unsigned)((count + per - 1) / per), (unsigned)n_streams), b((unsigned)std::min(256, (up + 63) / 64 * 64));
-        const size_t lds = (size_t)resample_lds_floats(up, down, J) * sizeof(float);
-        if (channels == 2)
-            hipLaunchKernelGGL((k_resample_phase<true, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
-                               m_first + count, dst_stride);
-        else
-            hipLaunchKernelGGL((k_resample_phase<false, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first,
-                               m_first + count, dst_stride);
-        return;
-    }
+    const ResLaunch pl = resample_launch_plan(up, down, J);
+    if (pl.path == kResReject) return;  // not from the engine: aid_resample refuses those with AID_ERR_INVALID
     const int64_t m_end = m_first + count;
-#ifndef AID_K6_NO_DEC  // diagnostic builds: MODE 2 for every decimation (A/B)
-    if (up == 1 && down == 3 && J == 61) {  // 48 kHz -> 16 kHz (browser capture -> the index rate)
-        const dim3 g((unsigned)((count + kDecThreads * kDecR - 1) / (kDecThreads * kDecR)), (unsigned)n_streams);
-        const size_t lds = (size_t)(dec_window<3, 61>() + 4) * sizeof(float);
-        if (channels == 2)
-            hipLaunchKernelGGL((k_decimate<true, 3, 61, T>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
-                               m_end, dst_stride);
-        else
-            hipLaunchKernelGGL((k_decimate<false, 3, 61, T>), g, dim3(kDecThreads), lds, s, in, hl, taps, dst, m_first,
-                               m_end, dst_stride);
-        return;
-    }
-#endif
-    const dim3 g((unsigned)((count + kResBlock - 1) / kResBlock), (unsigned)n_streams), b(kResThreads);
-    const size_t lds = (size_t)resample_lds_floats(up, down, J) * sizeof(float);
-    const int mode = up == 1 ? 2 : taps_in_lds(up, J) ? 1 : 0;
-#define AID_RS_LAUNCH(ST, MD) \
-    hipLaunchKernelGGL((k_resample<ST, MD, T>), g, b, lds, s, in, up, down, hl, J, taps, dst, m_first, m_end, dst_stride)
-    if (channels == 2) {
-        if (mode == 2) AID_RS_LAUNCH(true, 2); else if (mode == 1) AID_RS_LAUNCH(true, 1); else AID_RS_LAUNCH(true, 0);
-    } else {
-        if (mode == 2) AID_RS_LAUNCH(false, 2); else if (mode == 1) AID_RS_LAUNCH(false, 1); else AID_RS_LAUNCH(false, 0);
+    const dim3 g((unsigned)((count + pl.block - 1) / pl.block), (unsigned)n_streams), b((unsigned)pl.threads);
+    const size_t lds = (size_t)pl.lds_floats * sizeof(float);
+    const bool st = channels == 2;
+#define AID_RS_LAUNCH(KERNEL, ...) \
+    hipLaunchKernelGGL((KERNEL), g, b, lds, s, in, __VA_ARGS__, taps, dst, m_first, m_end, dst_stride)
+    switch (pl.path) {
+        case kResPhase:
+            if (st) AID_RS_LAUNCH((k_resample_phase<true, T>), up, down, hl, J);
+            else AID_RS_LAUNCH((k_resample_phase<false, T>), up, down, hl, J);
+            break;
+        case kResDecimate3:
+            if (st) AID_RS_LAUNCH((k_decimate<true, 3, 61, T>), hl);
+            else AID_RS_LAUNCH((k_decimate<false, 3, 61, T>), hl);
+            break;
+        case kResUniform:
+            if (st) AID_RS_LAUNCH((k_resample<true, 2, T>), up, down, hl, J);
+            else AID_RS_LAUNCH((k_resample<false, 2, T>), up, down, hl, J);
+            break;
+        case kResGlobalTaps:
+            if (st) AID_RS_LAUNCH((k_resample<true, 0, T>), up, down, hl, J);
+            else AID_RS_LAUNCH((k_resample<false, 0, T>), up, down, hl, J);
+            break;
+        default: break;
     }
 #undef AID_RS_LAUNCH
 }

@@ -11,9 +11,15 @@ import oracle as O
 
 RATES = [(48000, 16000), (48000, 44100), (44100, 16000), (16000, 48000), (44100, 48000), (22050, 16000),
          (96000, 44100), (8000, 44100)]
+# the other kinds of pair K6 has kernel forms for (tests/resample_cases.py): integer decimation other than 3, up 2,
+# the largest phase-major up, a filter of 9,421 taps, and up past the phase-major limit; with the input length of the
+# output comparison (a few thousand samples in or out; for the old pairs it stays sr_in // 3 + 17)
+PATH_RATES = {(32000, 16000): 4001, (96000, 16000): 6001, (15, 1): 6001, (1, 2): 3001, (695, 1024): 3001,
+              (471, 2): 40001, (1, 1025): 301}
+ALL_RATES = RATES + list(PATH_RATES)
 
 
-@pytest.mark.parametrize("sr_in,sr_out", RATES)
+@pytest.mark.parametrize("sr_in,sr_out", ALL_RATES)
 def test_taps_equal_scipy_firwin(sr_in, sr_out):
     up, down, hl, J = O.resample_ratio(sr_in, sr_out)
     h = ss.firwin(2 * hl + 1, 1.0 / max(up, down), window=("kaiser", 5.0)) * up
@@ -25,15 +31,39 @@ def test_taps_equal_scipy_firwin(sr_in, sr_out):
     assert ulps.max() <= 1
 
 
-@pytest.mark.parametrize("sr_in,sr_out", RATES)
+@pytest.mark.parametrize("sr_in,sr_out", ALL_RATES)
 def test_output_matches_scipy_resample_poly(sr_in, sr_out):
     rng = np.random.default_rng(sr_in + sr_out)
-    x = (rng.standard_normal(sr_in // 3 + 17) * 0.3).astype(np.float32)
+    x = (rng.standard_normal(PATH_RATES.get((sr_in, sr_out), sr_in // 3 + 17)) * 0.3).astype(np.float32)
     up, down, _, _ = O.resample_ratio(sr_in, sr_out)
     y = O.resample(x, sr_in, sr_out)
     yr = ss.resample_poly(x.astype(np.float64), up, down)
     assert len(y) == len(yr)
     assert np.max(np.abs(y - yr)) <= 2e-6 * (1 + np.max(np.abs(x)))
+
+
+def test_large_table_against_a_direct_binary64_sum():
+    """44101 -> 48000 (up 48,000, a table of 960,001 taps: too large for the scipy comparison to be quick): the
+    length, and the first and last 100 outputs against the same polyphase sum y[m] = sum_j h[p + j up] x[c / up - j],
+    c = m down + hl, p = c mod up, evaluated in binary64 with scipy's firwin taps. The bound is the other pairs'."""
+    sr_in, sr_out = 44101, 48000
+    up, down, hl, J = O.resample_ratio(sr_in, sr_out)
+    assert (up, down, hl, J) == (48000, 44101, 480000, 21)
+    rng = np.random.default_rng(sr_in + sr_out)
+    x = (rng.standard_normal(3001) * 0.3).astype(np.float32)
+    y = O.resample(x, sr_in, sr_out)
+    assert len(y) == -(-len(x) * up // down)
+    h = ss.firwin(2 * hl + 1, 1.0 / max(up, down), window=("kaiser", 5.0)) * up
+    xd = x.astype(np.float64)
+    for m in list(range(100)) + list(range(len(y) - 100, len(y))):
+        c = m * down + hl
+        p, i0 = c % up, c // up
+        ref = 0.0
+        for j in range(J):
+            k, i = p + j * up, i0 - j
+            if k <= 2 * hl and 0 <= i < len(x):
+                ref += h[k] * xd[i]
+        assert abs(y[m] - ref) <= 2e-6 * (1 + np.max(np.abs(x))), m
 
 
 def test_stereo_downmix_then_resample():
