@@ -24,15 +24,15 @@ AID_SYNTH_STATIONARY = 1
 AID_SYNTH_ASYNC = 2
 (AID_FORCE_K5_PATH, AID_FORCE_K5_PARTS, AID_FORCE_K5_BATCH, AID_FORCE_K2_STRIPS_X100, AID_FORCE_K4_BUILD,
  AID_FORCE_EXCHANGE_FAIL, AID_FORCE_LANE_GATHER, AID_FORCE_PLANE_ROWS, AID_FORCE_K2_WIDTH) = 1, 2, 3, 4, 5, 6, 7, 8, 9
-AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK, AID_FORCE_SPEED_GROUP = 10, 11, 12
+AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK, AID_FORCE_SPEED_GROUP, AID_FORCE_ROWS_MERGE = 10, 11, 12, 13
 AID_K_STFT, AID_K_PEAKS, AID_K_LANDMARK_COUNT, AID_K_LANDMARK_WRITE, AID_K_SYNTH, AID_K_MATCH = range(6)
-AID_K_RESAMPLE_SPEEDS, AID_K_SPEED_SELECT = 12, 13
-AID_K_COUNT = 14
+AID_K_RESAMPLE_SPEEDS, AID_K_SPEED_SELECT, AID_K_ROWS_MERGE, AID_K_INDEX_MERGE = 12, 13, 14, 15
+AID_K_COUNT = 16
 AID_MEL_FRAMES, AID_MEL_BANDS, AID_MEL_BINS, AID_MEL_WINDOW = 1001, 64, 513, 480000
 AID_MEL_ZERO, AID_MEL_REPEATPAD = 0, 1
 AID_MEL_BANK_SLANEY, AID_MEL_BANK_HTK, AID_MEL_BANK_CUSTOM = 0, 1, 2
 KERNEL_NAMES = ["stft_power", "peak_pick", "landmark_count", "landmark_write", "synth", "match", "resample",
-                "dedup", "index_build", "vote_hist", "hot_scan", "vote_final", "resample_speeds", "speed_select"]
+                "dedup", "index_build", "vote_hist", "hot_scan", "vote_final", "resample_speeds", "speed_select", "rows_merge", "index_merge"]
 
 
 class EngineUnavailable(RuntimeError):
@@ -147,6 +147,8 @@ SIGNATURES = [
     ("aid_index_remove", ctypes.c_int, [P, ctypes.c_uint32]),
     ("aid_index_compact", ctypes.c_int, [P, P]),
     ("aid_index_finalize", ctypes.c_int, [P]),
+    ("aid_index_live", ctypes.c_int, [P, I64]),
+    ("aid_index_live_stats", ctypes.c_int, [P, P, I32]),
     ("aid_index_stats", ctypes.c_int, [P, P, P, P]),
     ("aid_match_stats", ctypes.c_int, [P, P, I32, I32]),
     ("aid_index_export", ctypes.c_int, [P, P, P, P, I64, I64, I32]),

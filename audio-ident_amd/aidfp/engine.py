@@ -303,7 +303,7 @@ class Engine:
              "exchange_fail": L.AID_FORCE_EXCHANGE_FAIL, "lane_gather": L.AID_FORCE_LANE_GATHER,
              "plane_rows": L.AID_FORCE_PLANE_ROWS, "k2_width": L.AID_FORCE_K2_WIDTH,
              "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK,
-             "speed_group": L.AID_FORCE_SPEED_GROUP}
+             "speed_group": L.AID_FORCE_SPEED_GROUP, "rows_merge": L.AID_FORCE_ROWS_MERGE}
 
     def force(self, what: str, value: int) -> None:
         """Test hook (aid_engine_force): pin one of the engine's own code paths, e.g. force("k5_path", 2)."""
@@ -453,6 +453,22 @@ class Engine:
 
     def index_finalize(self) -> None:
         check(self._lib.aid_index_finalize(self._h))
+
+    LIVE_FALLBACKS = ("old_track", "compact", "reset", "load", "splice", "force", "removed")
+
+    def index_live(self, max_delta_postings: int) -> None:
+        """Ingest while serving (aid_index_live): with a cap > 0 the built CSR stays as the main segment and postings
+        stored since go into a small delta CSR, folded into main once they pass the cap; 0 turns it off."""
+        check(self._lib.aid_index_live(self._h, int(max_delta_postings)))
+
+    def index_live_stats(self) -> dict:
+        """aid_index_live_stats: builds of each kind, postings per segment, fall-backs to the full build by reason."""
+        out = np.zeros(6 + len(self.LIVE_FALLBACKS), dtype=np.int64)
+        check(self._lib.aid_index_live_stats(self._h, _p(out), len(out)))
+        d = dict(zip(("main_builds", "delta_builds", "folds", "main_postings", "delta_postings", "tracks_at_main"),
+                     (int(v) for v in out[:6])))
+        d["fallbacks"] = {k: int(v) for k, v in zip(self.LIVE_FALLBACKS, out[6:])}
+        return d
 
     def index_stats(self) -> dict:
         n = ctypes.c_int64()

@@ -113,6 +113,28 @@ def resolve_pcm_format(name: str | None = None) -> str:
     return fmt
 
 
+LIVE_INGEST_DEFAULT_CAP = 1 << 24  # postings the delta segment holds before it is folded (aidfp_live_plan.h)
+
+
+def resolve_live_ingest(value: int | None = None) -> int:
+    """The live-ingest postings cap of a service's engine (Engine.index_live; 0 = off): `value` if given (None = look
+    at env AIDFP_LIVE_INGEST, an int = that cap, 0 = off), else AIDFP_LIVE_INGEST: unset, "0" or "off" = off, "on" =
+    the default cap (2^24 postings), or a number of postings."""
+    if value is None:
+        text = (os.environ.get("AIDFP_LIVE_INGEST") or "off").strip().lower()
+        if text in ("0", "off"):
+            return 0
+        if text == "on":
+            return LIVE_INGEST_DEFAULT_CAP
+        try:
+            value = int(text)
+        except ValueError:
+            raise ValueError(f"AIDFP_LIVE_INGEST must be 0, off, on or a number of postings, got {text!r}") from None
+    if isinstance(value, bool) or int(value) < 0:
+        raise ValueError(f"live_ingest must be None or a postings cap >= 0, got {value!r}")
+    return int(value)
+
+
 def resolve_peak_rule(top_db: float | None = None, floor: float | None = None) -> dict:
     """The engine's peak rule as Engine keyword arguments (FPSPEC 5.1). top_db: the argument, else env
     AIDFP_PEAK_TOP_DB, else off (the absolute threshold, FPSPEC 5). floor: the argument, else env AIDFP_PEAK_FLOOR,
@@ -174,7 +196,11 @@ class FingerprintService:
     def __init__(self, db_dir: Path | None = None, device: int = -1, checkpoint_min_bytes: int = 64 << 20,
                  coalesce_window_s: float | None = None, max_batch: int = 256, max_batch_bytes: int = 64 << 20,
                  coalesce_workers: int = 1, pipeline: bool = True, split_min: int = 16, split_parts: int = 2,
-                 pcm_format: str | None = None, peak_top_db: float | None = None, peak_floor: float | None = None):
+                 pcm_format: str | None = None, peak_top_db: float | None = None, peak_floor: float | None = None,
+                 live_ingest: int | None = None):
+        # ingest while serving: a store no longer makes the next query batch rebuild the whole CSR (INTEGRATION.md,
+        # "Ingest while serving"). None = env AIDFP_LIVE_INGEST, else off; an int = the delta's postings cap
+        self.live_ingest = resolve_live_ingest(live_ingest)
         # the peak rule of this service's engine (resolve_peak_rule: arguments, else env AIDFP_PEAK_TOP_DB /
         # AIDFP_PEAK_FLOOR, else the FPSPEC 5 default); the index on disk does not record it
         self._peak_kw = resolve_peak_rule(peak_top_db, peak_floor)
@@ -249,6 +275,13 @@ class FingerprintService:
             except BaseException:
                 eng.close()
                 raise
+            # after the replay, which is a bulk load and ends in one main build at the first query
+            if self.live_ingest:
+                try:
+                    eng.index_live(self.live_ingest)
+                except EngineError as exc:
+                    eng.close()
+                    raise OlafError(f"cannot turn on live ingest: {exc}") from exc
             # the maps first, the engine last: _eng()'s lock-free fast path returns as soon as _engine is set,
             # and a reader that got it must find the names of the loaded tracks
             self._ids, self._names, self._next, self._store = ids, names, nxt, store

@@ -5,9 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <vector>
 
 #include "aidfp_buffers.h"
+#include "aidfp_live_plan.h"
 
 struct aid_engine;
 
@@ -23,6 +25,19 @@ struct CsrView {
     const uint8_t *tomb;      // per track id: 1 = removed
     uint32_t n_tracks;
     int check_tomb;  // tracks were removed after the build: the CSR still holds their postings
+};
+
+// One CSR over a contiguous range of the stored postings. The index has two (DESIGN 4b "Live ingest"): main over
+// postings [0, n_main), and, only while aid_index_live is on, delta over the tail [n_main, n_main + covered). A segment
+// is held through a shared_ptr: a ticket submitted with the feature on keeps the segments it was submitted under, and a
+// build that finds one of them still held builds into a fresh set of buffers instead of overwriting it.
+struct CsrSegment {
+    DevBuf<uint32_t> cnt, off;
+    DevBuf<uint64_t> post;
+    DevBuf<uint16_t> sig;
+    int64_t covered = 0;           // stored postings the build read
+    int64_t n_indexed = 0;         // postings in the CSR (removed tracks' postings dropped)
+    int64_t tomb_since_build = 0;  // removals after the build (queries must check tomb[])
 };
 
 struct HashIndex {
@@ -44,14 +59,18 @@ struct HashIndex {
     DevBuf<uint8_t> tomb;
     uint32_t n_tracks = 0;         // max track id + 1
     int64_t n_removed = 0;         // ones in h_tomb
-    int64_t tomb_since_build = 0;  // removals after the last CSR build (queries must check tomb[])
 
-    // CSR built from the postings
-    bool csr_current = false;  // built, and no posting, track or K4 knob changed since
-    int64_t n_indexed = 0;
-    DevBuf<uint32_t> idx_cnt, idx_off;
-    DevBuf<uint64_t> idx_post;
-    DevBuf<uint16_t> idx_sig;
+    // CSR built from the postings: main, and the delta of the live index
+    bool csr_current = false;  // main is built, and no posting it covers, no track of it and no K4 knob changed since
+    std::shared_ptr<CsrSegment> main = std::make_shared<CsrSegment>();
+    std::shared_ptr<CsrSegment> delta;  // exists only while live_cap > 0
+    std::shared_ptr<CsrSegment> spare;  // the main a fold replaced: the next fold's destination (live_cap > 0 only)
+    DevBuf<uint32_t> mrg_tot, mrg_items;  // K4m: the tiles' posting totals, the work items (MergeItem, 3 words each)
+    // live index (aid_index_live; policy: aidfp_live_plan.h)
+    int64_t live_cap = 0;         // max_delta_postings; 0 = off: every append clears csr_current, as ever
+    uint32_t tracks_at_main = 0;  // n_tracks at main's build: an append with only ids >= this keeps main
+    int64_t st_main_builds = 0, st_delta_builds = 0, st_folds = 0;
+    int64_t st_fallback[kLiveFallbacks] = {};
 
     // K4 scratch and knobs (aid_engine_force K4_BUILD)
     DevBuf<uint32_t> scan_tmp;
@@ -69,8 +88,24 @@ struct HashIndex {
     DevBuf<uint32_t> g_send, g_recv;   // all-gather: [3][max] SoA planes per rank
     int inject_exchange_fail = 0;      // aid_engine_force EXCHANGE_FAIL: the next exchange's prepare step fails (tests)
 
-    CsrView view() const {  // after ensure_index
-        return {idx_off.p, idx_post.p, idx_sig.p, tomb.p, n_tracks, tomb_since_build > 0};
+    CsrView view(const CsrSegment &g) const {  // after ensure_index
+        return {g.off.p, g.post.p, g.sig.p, tomb.p, n_tracks, g.tomb_since_build > 0};
+    }
+    CsrView view() const { return view(*main); }
+    LiveState live_state() const {  // n_post settled
+        return {live_cap, csr_current, main->covered, n_post, delta ? delta->covered : 0};
+    }
+    // a second K5 pass is due: the delta holds postings (after ensure_index)
+    bool delta_live() const { return live_cap > 0 && csr_current && delta && delta->covered > 0 && delta->n_indexed > 0; }
+    // an append of postings whose smallest track id is min_track: main stays current under the disjointness rule
+    void note_append(uint32_t min_track) {
+        if (live_append_keeps_main(live_cap, csr_current, min_track, tracks_at_main)) return;
+        drop_main(kFallOldTrack);
+    }
+    // main no longer describes the stored postings: the next query runs the full build
+    void drop_main(LiveFallback why) {
+        if (live_cap > 0 && csr_current) ++st_fallback[why];
+        csr_current = false;
     }
 };
 

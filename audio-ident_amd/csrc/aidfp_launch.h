@@ -82,4 +82,13 @@ struct MelTables;
 void launch_logmel(const void *pcm, bool s16, const MelChunkDev *chunks, int64_t chunk0, int64_t n, const MelTables *tab,
                    const float *wc, float *out, hipStream_t s);
 void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
+// the two row lists of each of nq queries over the live index merged into the first (index.hip k_rows_merge)
+void launch_rows_merge(int32_t *a, int32_t *na, const int32_t *b, const int32_t *nb, int nq, int mr, hipStream_t s);
+// K4m csr_merge (index_merge.hip): the folded CSR's offsets, the tiles' posting totals, and the merge over the work
+// items of aidfp_live_plan.h plan_merge (items: device MergeItem[n_items])
+void launch_csr_merge_offsets(const uint32_t *om, const uint32_t *od, uint32_t *on, int64_t n, hipStream_t s);
+void launch_csr_merge_totals(const uint32_t *om, const uint32_t *od, uint32_t *total, int n_tiles, hipStream_t s);
+void launch_csr_merge(const void *items, int64_t n_items, const uint32_t *om, const uint64_t *pm, const uint16_t *sm,
+                      const uint32_t *od, const uint64_t *pd, const uint16_t *sd, uint64_t *pn, uint16_t *sn,
+                      hipStream_t s);
 }  // namespace aid

@@ -183,7 +183,7 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
                 return fail(AID_ERR_INVALID, "K4_BUILD: 0 default, 1 radix, 2 atomic, 4 radix with ballot ranks");
             e->idx.k4_build = value == 2 ? K4Build::kAtomic : K4Build::kRadix;
             e->idx.k4_rank = value == 4 ? 1 : 0;
-            e->idx.csr_current = false;
+            e->idx.drop_main(kFallForce);
             return AID_OK;
         case AID_FORCE_EXCHANGE_FAIL:
             if (value != 0 && value != 1) return fail(AID_ERR_INVALID, "EXCHANGE_FAIL: 0 or 1");
@@ -209,6 +209,10 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
         case AID_FORCE_SPEED_GROUP:
             if (value < 0) return fail(AID_ERR_INVALID, "SPEED_GROUP must be >= 0");
             e->speed_group = value;
+            return AID_OK;
+        case AID_FORCE_ROWS_MERGE:
+            if (value != 0 && value != 1) return fail(AID_ERR_INVALID, "ROWS_MERGE: 0 or 1");
+            e->rows_merge_dev = value;
             return AID_OK;
         default:
             return fail(AID_ERR_INVALID, "aid_engine_force: unknown path id");

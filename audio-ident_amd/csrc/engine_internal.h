@@ -49,6 +49,16 @@ struct K5Host {
     HostBuf<int32_t> nrows;  // the LDS pass's row counts; -r: handed back for reason r (index.hip)
 };
 
+// K5's device scratch of one pass over one CSR segment: the queries' exact votes, the CSR range of every query record
+// (k_query_votes -> k_match_lds), and the pass's rows and row counts. The engine owns one per segment: the two passes
+// of a query over the live index are queued back to back, and a set shared between them would be overwritten by the
+// second before the first one's results were copied out
+struct K5Scratch {
+    DevBuf<int64_t> votes;    // exact votes per query (LDS-histogram eligibility)
+    DevBuf<uint64_t> ranges;  // per query record its CSR range
+    DevBuf<int32_t> rows, nrows;  // [nq][max_results][5], [nq]
+};
+
 struct ProfEvent {
     int kernel;
     hipEvent_t a, b;
@@ -75,6 +85,11 @@ struct aid_query_ticket {
     hipStream_t s = nullptr;
     Event ev;
     K5Host host;  // the LDS pass's results, complete behind ev
+    // live index (aid_index_live on at submit): the delta pass's results, and the segments the ticket was submitted
+    // under, held until it is collected (a build meanwhile leaves them alone, aidfp_index.h CsrSegment)
+    K5Host host_d;
+    bool two = false;  // a delta pass was queued
+    std::shared_ptr<CsrSegment> seg_main, seg_delta;
     DevBuf<uint64_t> recs;
     DevBuf<int64_t> qsc;  // device record starts and counts of the ticket's queries ([0, nq), [nq, 2nq))
 };
@@ -96,15 +111,13 @@ struct aid_engine {
     DevBuf<uint64_t> q_recs;
     DevBuf<int64_t> q_start, q_count;
     DevBuf<uint32_t> q_hist;
-    DevBuf<int32_t> q_rows, q_nrows;
+    K5Scratch q, qd;  // K5 scratch of the main pass and of the live index's delta pass
     DevBuf<uint32_t> q_hot;  // K5h hot-bucket bitmaps, [batch][2^bits / 32]
     DevBuf<uint32_t> q_dset;  // K5b retries: HBM distinct (slot, t_q) sets, [batch][2^dbits]
-    DevBuf<uint64_t> q_ranges;  // K5: per query record its CSR range (k_query_votes -> k_match_lds)
-    K5Host k5h;                 // run_queries: the synchronous calls' result block
+    K5Host k5h, k5h_d;          // run_queries: the synchronous calls' result blocks (main pass, delta pass)
     HostBuf<int64_t> hq_start;  // the queries' record starts (clip_base) staged page-locked for their upload
     // collected tickets, reused: their buffers and event stay allocated
     std::vector<std::unique_ptr<aid_query_ticket>> ticket_pool;
-    DevBuf<int64_t> q_votes;  // exact votes per query (LDS-histogram eligibility)
     DevBuf<int64_t> q_gsc;    // K5 global pass: record starts and counts of the queries it runs ([0, n), [n, 2n))
     DevBuf<int32_t> q_grows;  // K5 global pass: their rows [n][max_results][5], then their n row counts
     // batched exact lane (aid_exact_lane): PCM staging, window descriptors, consensus output
@@ -142,6 +155,7 @@ struct aid_engine {
     int k5_path = 0;
     int k5_parts = 0;      // aid_engine_force K5_PARTS: K5a key partitions per query (0 = by vote count)
     int lane_gather = 0;           // aid_engine_force LANE_GATHER: stage the exact lane's sub-windows (A/B)
+    int rows_merge_dev = 0;        // aid_engine_force ROWS_MERGE: host-row calls merge two-segment rows on the device
     // aid_match_stats: queries, exact votes, and the postings K5 read (a vote = one 8-B posting per pass)
     int64_t st_queries = 0, st_votes = 0, st_post_reads = 0, st_q_global = 0, st_q_lds = 0, st_records = 0;
     int64_t st_sig_reads = 0;  // 2-B posting signatures the LDS path read (two per vote: counting and insert passes)

@@ -25,6 +25,7 @@
 //        histogram row for the next batch.
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
+#include "aidfp_live_plan.h"
 
 namespace aid {
 
@@ -1148,6 +1149,48 @@ void launch_index_checksum(const uint32_t *ph, const uint32_t *ptr, const uint32
     if (n <= 0) return;
     const int64_t blocks = std::min<int64_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_index_checksum, dim3((unsigned)blocks), dim3(256), 0, s, ph, ptr, pt, first, n, out);
+}
+
+// `rows_merge`: the rows of a query over the live index's two segments made one list (DESIGN 4b "Live ingest"). Query
+// q has na[q] rows in a[q][mr][5] (the main pass's slot) and nb[q] in b[q][mr][5], each in rank order; the merged
+// top mr replace a's rows and na[q]. One wave per query, kMergeWaves queries per workgroup: the wave stages both lists
+// in LDS with coalesced loads, its first lane runs merge_rows (aidfp_live_plan.h, the one statement of the rule; at
+// most 2 mr row moves, out of LDS) and the wave stores the result. Lists too long for the staging (mr above
+// kMergeLdsRows) are merged in place in global memory by the first lane alone.
+constexpr int kMergeWaves = 4;
+constexpr int kMergeLdsRows = 256;  // rows per list staged in LDS: 4 waves x 2 lists x 256 rows x 20 B = 40 KB
+
+__global__ __launch_bounds__(64 * kMergeWaves) void k_rows_merge(int32_t *__restrict__ a, int32_t *__restrict__ na,
+                                                                 const int32_t *__restrict__ b,
+                                                                 const int32_t *__restrict__ nb, int nq, int mr) {
+    extern __shared__ int32_t s_merge[];  // [kMergeWaves][2][mr][5], or nothing above kMergeLdsRows
+    __shared__ int s_total[kMergeWaves];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * kMergeWaves + w;
+    const bool live = q < nq;
+    const bool staged = mr <= kMergeLdsRows;
+    const size_t row0 = (size_t)(live ? q : 0) * mr * kRowWords;
+    const int ca = live ? min(max(na[q], 0), mr) : 0, cb = live ? min(max(nb[q], 0), mr) : 0;
+    int32_t *sa = s_merge + (size_t)w * 2 * mr * kRowWords, *sb = sa + (size_t)mr * kRowWords;
+    if (staged) {
+        for (int i = lane; i < ca * kRowWords; i += 64) sa[i] = a[row0 + i];
+        for (int i = lane; i < cb * kRowWords; i += 64) sb[i] = b[row0 + i];
+    }
+    __syncthreads();
+    if (live && lane == 0) s_total[w] = staged ? merge_rows(sa, ca, sb, cb, mr) : merge_rows(a + row0, ca, b + row0, cb, mr);
+    __syncthreads();
+    if (!live) return;
+    const int total = s_total[w];
+    if (staged)
+        for (int i = lane; i < total * kRowWords; i += 64) a[row0 + i] = sa[i];
+    if (lane == 0) na[q] = total;
+}
+
+void launch_rows_merge(int32_t *a, int32_t *na, const int32_t *b, const int32_t *nb, int nq, int mr, hipStream_t s) {
+    if (nq <= 0) return;
+    const uint32_t shm = mr <= kMergeLdsRows ? (uint32_t)(kMergeWaves * 2 * mr * kRowWords * sizeof(int32_t)) : 0u;
+    timed_launch(k_rows_merge, dim3((unsigned)((nq + kMergeWaves - 1) / kMergeWaves)), dim3(64 * kMergeWaves), shm, s, a, na,
+                 b, nb, nq, mr);
 }
 
 uint32_t index_keys() { return kKeys; }

@@ -132,7 +132,7 @@ static int splice_locked(aid_engine *e, int64_t first, const uint32_t *recv, int
     }
     HIP_TRY(hipStreamSynchronize(s));
     e->idx.n_post = at;
-    e->idx.csr_current = false;
+    e->idx.drop_main(kFallSplice);
     return AID_OK;
 }
 

@@ -1,7 +1,8 @@
 // index_host.cpp -- host side of the hash index (spec/FPSPEC.md 7; state: struct HashIndex, aidfp_index.h): the
 // posting planes and their asynchronous append, the track table, K4's CSR build, and the aid_index_* entry points
-// that store, remove, compact, build, read back, save and load. The exchange between ranks is index_exchange.cpp;
-// K5 reads the built CSR through HashIndex::view() (query.cpp).
+// that store, remove, compact, build, read back, save and load, and the live index's two CSR segments (aid_index_live:
+// main, the delta of the postings stored since, the fold K4m; policy in aidfp_live_plan.h). The exchange between ranks
+// is index_exchange.cpp; K5 reads a built CSR segment through HashIndex::view() (query.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -73,8 +74,8 @@ int aid_index_reset(aid_engine *e) {
     ix.n_tracks = 0;
     ix.h_tomb.clear();
     ix.n_removed = 0;
-    ix.csr_current = false;
-    ix.n_indexed = 0;
+    ix.drop_main(kFallReset);
+    ix.main->n_indexed = 0;
     return AID_OK;
 }
 
@@ -98,11 +99,12 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
     HIP_TRY(ix.h_stage.reserve(3 * (size_t)n + (size_t)n / 2 + 1));
     int64_t *counts = ix.h_stage.p, *src = counts + n, *dst = src + n;
     uint32_t *trk = reinterpret_cast<uint32_t *>(dst + n);
-    uint32_t mx = 0;
+    uint32_t mx = 0, mn = 0xFFFFFFFFu;
     for (int c = 0; c < n; ++c) {
         src[c] = e->ext.plan.hash_base[c];
         trk[c] = track_ids[c];
         mx = std::max(mx, track_ids[c] + 1);
+        mn = std::min(mn, track_ids[c]);
     }
     if (int rc = ensure_tracks(e, mx, s)) return rc;
     HIP_TRY(ix.x_src.reserve(n));
@@ -148,7 +150,7 @@ int aid_index_add_extracted(aid_engine *e, const uint32_t *track_ids) {
         HIP_TRY(hipGetLastError());  // no sync: every reader of the posting planes syncs last_stream first
         ix.n_post += tot;
     }
-    ix.csr_current = false;
+    ix.note_append(mn);
     return AID_OK;
 }
 
@@ -163,14 +165,20 @@ int aid_index_add_postings(aid_engine *e, const uint32_t *hash, const uint32_t *
     hipStream_t s = call.s;
     // the largest track id; 0xFFFFFFFF is K5's empty-slot marker (with d = -1 also the empty (track, d) key), and
     // id + 1 would wrap to 0: rejected before anything is grown or copied, as in aid_index_add_track
-    uint32_t top = 0;
+    uint32_t top = 0, low = 0xFFFFFFFFu;  // low: the live index's disjointness rule (aidfp_live_plan.h)
     if (location == AID_PCM_HOST) {
-        for (int64_t i = 0; i < n; ++i) top = std::max(top, track[i]);
+        for (int64_t i = 0; i < n; ++i) {
+            top = std::max(top, track[i]);
+            low = std::min(low, track[i]);
+        }
     } else {
         // device track ids: one max-reduction via a host copy of the track column
         std::vector<uint32_t> tr(n);
         HIP_TRY(hipMemcpy(tr.data(), track, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < n; ++i) top = std::max(top, tr[i]);
+        for (int64_t i = 0; i < n; ++i) {
+            top = std::max(top, tr[i]);
+            low = std::min(low, tr[i]);
+        }
     }
     if (top == 0xFFFFFFFFu) return fail(AID_ERR_INVALID, "aid_index_add_postings: bad track id");
     const uint32_t mx = top + 1;
@@ -182,7 +190,7 @@ int aid_index_add_postings(aid_engine *e, const uint32_t *hash, const uint32_t *
     HIP_TRY(hipMemcpyAsync(ix.p_t.p + ix.n_post, t, n * sizeof(uint32_t), k, s));
     HIP_TRY(hipStreamSynchronize(s));
     ix.n_post += n;
-    ix.csr_current = false;
+    ix.note_append(low);
     return AID_OK;
 }
 
@@ -203,7 +211,8 @@ int aid_index_remove(aid_engine *e, uint32_t track) {
     if (track >= ix.n_tracks || ix.h_tomb[track]) return fail(AID_ERR_INVALID, "track not indexed");
     ix.h_tomb[track] = 1;
     ++ix.n_removed;
-    ++ix.tomb_since_build;  // the CSR still holds its postings until the next finalize
+    ++ix.main->tomb_since_build;  // the CSRs still hold its postings until their next builds
+    if (ix.delta) ++ix.delta->tomb_since_build;
     HIP_TRY(hipMemcpy(ix.tomb.p + track, &ix.h_tomb[track], 1, hipMemcpyHostToDevice));
     return AID_OK;
 }
@@ -238,61 +247,63 @@ int aid_index_compact(aid_engine *e, int64_t *n_removed) {
     std::swap(ix.p_track, ntr);
     std::swap(ix.p_t, nt);  // the old planes are released with the scratch buffers
     ix.n_post = live;  // tombstones stay: removed ids are never reused, and the CSR skips nothing new
-    ix.csr_current = false;
+    ix.drop_main(kFallCompact);
     return AID_OK;
 }
 
-// K4: the CSR (offsets, postings, signatures) built from the stored postings. Engine lock held, the append settled
-// and last_stream drained
-static int build_csr(aid_engine *e) {
+// K4: the CSR (offsets, postings, signatures) of segment `seg` built from the stored postings [first, first + count).
+// Engine lock held, the append settled and last_stream drained. A segment a ticket still holds is left to it and
+// a fresh one built (aidfp.h, "Ingest while serving")
+static int build_csr(aid_engine *e, std::shared_ptr<CsrSegment> &seg, int64_t first, int64_t count) {
     HashIndex &ix = e->idx;
     hipStream_t s = e->own_stream;
     if (ix.n_post > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index holds more than 2^32 postings");
+    if (seg.use_count() > 1) seg = std::make_shared<CsrSegment>();
+    CsrSegment &g = *seg;
+    const uint32_t *p_hash = ix.p_hash.p + first, *p_track = ix.p_track.p + first, *p_t = ix.p_t.p + first;
     const size_t K = (size_t)index_keys() + 1;
-    HIP_TRY(ix.idx_cnt.reserve(K));
-    HIP_TRY(ix.idx_off.reserve(K));
+    HIP_TRY(g.cnt.reserve(K));
+    HIP_TRY(g.off.reserve(K));
     HIP_TRY(ix.scan_tmp.reserve(4 * (K / 1024 + 2) + 4096));
-    HIP_TRY(ix.idx_post.reserve((size_t)std::max<int64_t>(ix.n_post, 1)));
+    HIP_TRY(g.post.reserve((size_t)std::max<int64_t>(count, 1)));
     // + 8: K5's LDS path reads the signatures in aligned chunks of 4 or 8; a record's last chunk may reach past the end
-    HIP_TRY(ix.idx_sig.reserve((size_t)std::max<int64_t>(ix.n_post, 1) + 8));
+    HIP_TRY(g.sig.reserve((size_t)std::max<int64_t>(count, 1) + 8));
     if (ix.n_tracks == 0) HIP_TRY(ix.tomb.reserve(1024));
-    HIP_TRY(hipMemsetAsync(ix.idx_cnt.p, 0, K * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(g.cnt.p, 0, K * sizeof(uint32_t), s));
     HIP_TRY(ix.nz.reserve(1));
     HIP_TRY(hipMemsetAsync(ix.nz.p, 0, sizeof(unsigned long long), s));
-    if (ix.k4_build == K4Build::kRadix && ix.n_post > 0) {
+    if (ix.k4_build == K4Build::kRadix && count > 0) {
         // sort build (index_sort.hip): stable radix sort of (key27, track | t << 32) -> run ends -> max-scan
-        const size_t np = (size_t)ix.n_post;
-        HIP_TRY(ix.srt_scratch.reserve(radix_scratch_u32(ix.n_post)));
+        const size_t np = (size_t)count;
+        HIP_TRY(ix.srt_scratch.reserve(radix_scratch_u32(count)));
         HIP_TRY(ix.srt_k0.reserve(np));
         HIP_TRY(ix.srt_k1.reserve(np));
         HIP_TRY(ix.srt_v.reserve(np));
         uint64_t *sorted = nullptr;
         {
             ProfScope ps(e, AID_K_INDEX_BUILD, s);
-            HIP_TRY(launch_index_sort_build(ix.p_hash.p, ix.p_track.p, ix.p_t.p, ix.n_post,
-                                            ix.n_removed ? ix.tomb.p : nullptr, ix.n_tracks, ix.srt_k0.p, ix.srt_k1.p,
-                                            ix.srt_v.p, ix.idx_post.p, ix.srt_scratch.p, ix.idx_cnt.p, ix.idx_off.p,
-                                            ix.nz.p, &sorted, ix.idx_sig.p, ix.k4_rank, s));
-            if (sorted == ix.srt_v.p) std::swap(ix.srt_v, ix.idx_post);  // the CSR's post array is where the sort ended
+            HIP_TRY(launch_index_sort_build(p_hash, p_track, p_t, count, ix.n_removed ? ix.tomb.p : nullptr, ix.n_tracks,
+                                            ix.srt_k0.p, ix.srt_k1.p, ix.srt_v.p, g.post.p, ix.srt_scratch.p, g.cnt.p,
+                                            g.off.p, ix.nz.p, &sorted, g.sig.p, ix.k4_rank, s));
+            if (sorted == ix.srt_v.p) std::swap(ix.srt_v, g.post);  // the CSR's post array is where the sort ended
         }
     } else {
-        launch_index_count(ix.p_hash.p, ix.p_track.p, ix.n_post, ix.tomb.p, ix.n_tracks, ix.idx_cnt.p, s);
-        launch_count_nonzero(ix.idx_cnt.p, (int64_t)K, ix.nz.p, s);
-        launch_scan(ix.idx_cnt.p, ix.idx_off.p, (int64_t)K, ix.scan_tmp.p, s);
-        HIP_TRY(hipMemcpyAsync(ix.idx_cnt.p, ix.idx_off.p, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        launch_index_scatter(ix.p_hash.p, ix.p_track.p, ix.p_t.p, ix.n_post, ix.tomb.p, ix.n_tracks, ix.idx_cnt.p,
-                             ix.idx_post.p, s);
-        launch_make_sig(ix.idx_post.p, ix.n_post, ix.idx_sig.p, s);  // (only the first n_indexed are read)
+        launch_index_count(p_hash, p_track, count, ix.tomb.p, ix.n_tracks, g.cnt.p, s);
+        launch_count_nonzero(g.cnt.p, (int64_t)K, ix.nz.p, s);
+        launch_scan(g.cnt.p, g.off.p, (int64_t)K, ix.scan_tmp.p, s);
+        HIP_TRY(hipMemcpyAsync(g.cnt.p, g.off.p, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        launch_index_scatter(p_hash, p_track, p_t, count, ix.tomb.p, ix.n_tracks, g.cnt.p, g.post.p, s);
+        launch_make_sig(g.post.p, count, g.sig.p, s);  // (only the first n_indexed are read)
     }
     HIP_TRY(hipGetLastError());
     uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, ix.idx_off.p + (K - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&total, g.off.p + (K - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    ix.n_indexed = total;
-    ix.csr_current = true;
-    ix.tomb_since_build = 0;  // the build skipped every removed track's postings
+    g.covered = count;
+    g.n_indexed = total;
+    g.tomb_since_build = 0;  // the build skipped every removed track's postings
     // the sort's double buffers are 16 B per posting (15 GB at the 100k-track catalog): kept for the next build
-    // of a small index (a store + query cycle rebuilds it), released above 1 GiB
+    // of a small index (a store + query cycle rebuilds it, or its delta), released above 1 GiB
     if ((ix.srt_k0.n + ix.srt_k1.n) * 4 + ix.srt_v.n * 8 + ix.srt_scratch.n * 4 > ((size_t)1 << 30)) {
         ix.srt_k0.release();
         ix.srt_k1.release();
@@ -302,9 +313,129 @@ static int build_csr(aid_engine *e) {
     return AID_OK;
 }
 
+static void empty_delta(HashIndex &ix) {
+    if (!ix.delta) return;
+    if (ix.delta.use_count() > 1) ix.delta = std::make_shared<CsrSegment>();  // a ticket keeps the old one
+    ix.delta->covered = ix.delta->n_indexed = ix.delta->tomb_since_build = 0;
+}
+
+// The full build: main over every stored posting, the delta emptied
+static int build_main(aid_engine *e) {
+    HashIndex &ix = e->idx;
+    if (int rc = build_csr(e, ix.main, 0, ix.n_post)) return rc;
+    ix.csr_current = true;
+    ix.tracks_at_main = ix.n_tracks;
+    ++ix.st_main_builds;
+    empty_delta(ix);
+    return AID_OK;
+}
+
+// the delta over the tail [n_main, n_post): K4 unchanged, on the planes from n_main on
+static int build_delta(aid_engine *e) {
+    HashIndex &ix = e->idx;
+    if (!ix.delta) ix.delta = std::make_shared<CsrSegment>();
+    if (int rc = build_csr(e, ix.delta, ix.main->covered, ix.n_post - ix.main->covered)) return rc;
+    ++ix.st_delta_builds;
+    return AID_OK;
+}
+
+// The fold (K4m, index_merge.hip): the delta, built over the whole tail first, merged into main without a sort. The
+// merged CSR goes into a second set of buffers (the main the last fold replaced, if no ticket holds it) and becomes
+// main. With no track removed since main's build it equals the full build's CSR bit for bit; removed tracks' postings
+// are carried along and check_tomb stays set for them
+static int fold_delta(aid_engine *e) {
+    HashIndex &ix = e->idx;
+    hipStream_t s = e->own_stream;
+    if (ix.n_post > 0xFFFFFFFFll) return fail(AID_ERR_INVALID, "index holds more than 2^32 postings");
+    if (!ix.delta || ix.delta->covered != ix.n_post - ix.main->covered)
+        if (int rc = build_delta(e)) return rc;
+    std::shared_ptr<CsrSegment> out = ix.spare && ix.spare.use_count() == 1 ? std::move(ix.spare) : std::make_shared<CsrSegment>();
+    ix.spare.reset();
+    const CsrSegment &m = *ix.main, &d = *ix.delta;
+    const int64_t n = m.n_indexed + d.n_indexed;
+    const size_t K = (size_t)index_keys() + 1;
+    const int n_tiles = (int)(index_keys() / kMergeTileKeys);
+    HIP_TRY(out->off.reserve(K));
+    HIP_TRY(out->post.reserve((size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(out->sig.reserve((size_t)std::max<int64_t>(n, 1) + 8));  // + 8: as build_csr
+    HIP_TRY(ix.mrg_tot.reserve((size_t)n_tiles));
+    std::vector<uint32_t> tot((size_t)n_tiles);
+    std::vector<MergeItem> items;
+    {
+        ProfScope ps(e, AID_K_INDEX_MERGE, s);
+        launch_csr_merge_offsets(m.off.p, d.off.p, out->off.p, (int64_t)K, s);
+        launch_csr_merge_totals(m.off.p, d.off.p, ix.mrg_tot.p, n_tiles, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(tot.data(), ix.mrg_tot.p, tot.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        items.resize((size_t)plan_merge(tot.data(), n_tiles, kMergeItemPosts, nullptr));
+        plan_merge(tot.data(), n_tiles, kMergeItemPosts, items.data());
+        if (!items.empty()) {
+            static_assert(sizeof(MergeItem) == 3 * sizeof(uint32_t), "MergeItem is three words");
+            HIP_TRY(ix.mrg_items.reserve(3 * items.size()));
+            HIP_TRY(hipMemcpyAsync(ix.mrg_items.p, items.data(), items.size() * sizeof(MergeItem), hipMemcpyHostToDevice, s));
+            launch_csr_merge(ix.mrg_items.p, (int64_t)items.size(), m.off.p, m.post.p, m.sig.p, d.off.p, d.post.p, d.sig.p,
+                             out->post.p, out->sig.p, s);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));  // (the items are pageable host memory)
+    out->covered = ix.n_post;
+    out->n_indexed = n;
+    out->tomb_since_build = m.tomb_since_build + d.tomb_since_build;
+    std::shared_ptr<CsrSegment> old = std::move(ix.main);
+    ix.main = std::move(out);
+    if (old.use_count() == 1) ix.spare = std::move(old);  // no ticket holds it: the next fold's destination
+    empty_delta(ix);
+    ix.csr_current = true;
+    ix.tracks_at_main = ix.n_tracks;
+    ++ix.st_folds;
+    return AID_OK;
+}
+
 int aid_index_finalize(aid_engine *e) {
     EngineCall call(e, nullptr, true, kDrainLast);
-    return call.rc ? call.rc : build_csr(e);
+    if (call.rc) return call.rc;
+    HashIndex &ix = e->idx;
+    // always one CSR over everything: a live delta is folded, or, with a track removed since main's build, rebuilt
+    // with main (the full build drops that track's postings; a fold would carry them)
+    if (ix.live_cap > 0 && ix.csr_current && ix.n_post > ix.main->covered) {
+        if (ix.main->tomb_since_build == 0) return fold_delta(e);
+        ++ix.st_fallback[kFallRemoved];
+    }
+    return build_main(e);
+}
+
+int aid_index_live(aid_engine *e, int64_t max_delta_postings) {
+    if (max_delta_postings < 0) return fail(AID_ERR_INVALID, "aid_index_live: max_delta_postings must be >= 0");
+    EngineCall call(e, nullptr, true, kDrainLast);
+    if (call.rc) return call.rc;
+    HashIndex &ix = e->idx;
+    if (max_delta_postings == ix.live_cap) return AID_OK;
+    if (ix.csr_current && ix.n_post > ix.main->covered)  // a change while a delta is live folds first
+        if (int rc = fold_delta(e)) return rc;
+    ix.live_cap = max_delta_postings;
+    if (ix.live_cap == 0) {  // (a ticket that holds the delta keeps it until it is collected)
+        ix.delta.reset();
+        ix.spare.reset();
+    }
+    return AID_OK;
+}
+
+int aid_index_live_stats(aid_engine *e, int64_t *out, int32_t n) {
+    if (n < 0 || (n > 0 && !out)) return fail(AID_ERR_INVALID, "aid_index_live_stats: bad argument");
+    EngineCall call(e, nullptr, true);
+    if (call.rc) return call.rc;
+    const HashIndex &ix = e->idx;
+    int64_t v[kLiveStatsWords] = {ix.st_main_builds,
+                                  ix.st_delta_builds,
+                                  ix.st_folds,
+                                  ix.csr_current ? ix.main->covered : 0,
+                                  ix.csr_current ? ix.n_post - ix.main->covered : 0,
+                                  (int64_t)ix.tracks_at_main};
+    for (int r = 0; r < kLiveFallbacks; ++r) v[6 + r] = ix.st_fallback[r];
+    for (int i = 0; i < n && i < kLiveStatsWords; ++i) out[i] = v[i];
+    return AID_OK;
 }
 
 int aid_index_stats(aid_engine *e, int64_t *n_postings, int64_t *n_live, uint32_t *n_tracks) {
@@ -312,7 +443,10 @@ int aid_index_stats(aid_engine *e, int64_t *n_postings, int64_t *n_live, uint32_
     if (call.rc) return call.rc;
     const HashIndex &ix = e->idx;
     if (n_postings) *n_postings = ix.n_post;
-    if (n_live) *n_live = ix.csr_current ? ix.n_indexed : -1;
+    // both segments' postings; stale (-1) also while stored postings wait for their delta build
+    const int64_t tail = ix.csr_current ? ix.n_post - ix.main->covered : 0;
+    const bool stale = !ix.csr_current || (tail > 0 && (!ix.delta || ix.delta->covered != tail));
+    if (n_live) *n_live = stale ? -1 : ix.main->n_indexed + (tail > 0 ? ix.delta->n_indexed : 0);
     if (n_tracks) *n_tracks = ix.n_tracks;
     return AID_OK;
 }
@@ -361,16 +495,19 @@ int aid_index_csr_export(aid_engine *e, uint32_t *offsets, int64_t n_offsets, ui
     if (call.rc) return call.rc;
     const HashIndex &ix = e->idx;
     if (!ix.csr_current) return fail(AID_ERR_STATE, "aid_index_csr_export: the index is not finalized");
+    if (ix.n_post > ix.main->covered)
+        return fail(AID_ERR_STATE, "aid_index_csr_export: postings stored since the last build are in the live delta "
+                                   "segment (aid_index_live); call aid_index_finalize for one CSR over everything");
     if (int rc = EngineCall::wait_last(e, call.s, kDrainLast)) return rc;
     const int64_t K = (int64_t)index_keys() + 1;
-    *n_out = ix.n_indexed;
+    *n_out = ix.main->n_indexed;
     if (offsets && n_offsets > 0) {
         if (n_offsets < K) return fail(AID_ERR_INVALID, "aid_index_csr_export: offsets need 2^26 + 1 entries");
-        HIP_TRY(hipMemcpy(offsets, ix.idx_off.p, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(offsets, ix.main->off.p, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     if (posts && cap > 0) {
-        const int64_t n = std::min<int64_t>(cap, ix.n_indexed);
-        if (n > 0) HIP_TRY(hipMemcpy(posts, ix.idx_post.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        const int64_t n = std::min<int64_t>(cap, ix.main->n_indexed);
+        if (n > 0) HIP_TRY(hipMemcpy(posts, ix.main->post.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return AID_OK;
 }
@@ -456,15 +593,20 @@ int aid_index_load(aid_engine *e, const char *path) {
     ix.n_removed = (int64_t)ix.h_tomb.size() - std::count(ix.h_tomb.begin(), ix.h_tomb.end(), 0);
     ix.n_tracks = nt;
     ix.n_post = n;
-    ix.tomb_since_build = 0;
-    ix.csr_current = false;
+    ix.main->tomb_since_build = 0;
+    ix.drop_main(kFallLoad);
     return AID_OK;
 }
 
 }  // extern "C"
 
 int ensure_index(aid_engine *e) {
-    if (e->idx.csr_current) return AID_OK;
+    HashIndex &ix = e->idx;
+    if (ix.csr_current && ix.live_cap == 0) return AID_OK;
+    if (int rc = settle_postings(e)) return rc;
+    const LiveStep step = live_step(ix.live_state());
+    if (step == kLiveKeep) return AID_OK;
     if (int rc = EngineCall::enter(e, e->own_stream, true, kDrainLast)) return rc;
-    return build_csr(e);
+    if (step == kLiveDelta) return build_delta(e);
+    return step == kLiveFold ? fold_delta(e) : build_main(e);
 }

@@ -33,43 +33,47 @@ constexpr double kForwardedPerBucket = 2.0;  // forwarded votes (1-bit filter es
 // Phase 1, no synchronisation: the vote counts of nq queries whose records are at device ranges (qstart_dev /
 // qcount_dev), with `lds` the LDS pass, and the copies of starts, counts, votes and the pass's results into `h`.
 // rec_cap: elements of `recs` (the CSR range cache the vote count writes for the LDS pass has one entry per record
-// index). want_rows = false (device mode): the rows stay in e->q_rows. have_starts: h.meta already holds the starts.
-static int k5_enqueue(aid_engine *e, const uint64_t *recs, const int64_t *qstart_dev, const int64_t *qcount_dev, int nq,
-                      int64_t rec_cap, bool lds, bool want_rows, K5Host &h, hipStream_t s, bool have_starts = false) {
+// index). want_rows = false (device mode): the rows stay in sc.rows. have_starts: h.meta already holds the starts.
+// The pass reads the CSR segment `ix` and works in the scratch `sc` (one per segment: engine_internal.h).
+static int k5_enqueue(aid_engine *e, const CsrView &ix, K5Scratch &sc, const uint64_t *recs, const int64_t *qstart_dev,
+                      const int64_t *qcount_dev, int nq, int64_t rec_cap, bool lds, bool want_rows, K5Host &h,
+                      hipStream_t s, bool have_starts = false) {
     const int mr = e->cfg.max_results;
-    const CsrView ix = e->idx.view();
-    HIP_TRY(e->q_rows.reserve((size_t)std::max(nq, 1) * mr * 5));
-    HIP_TRY(e->q_nrows.reserve((size_t)std::max(nq, 1)));
-    HIP_TRY(e->q_votes.reserve((size_t)nq));
-    if (lds) HIP_TRY(e->q_ranges.reserve((size_t)std::max<int64_t>(rec_cap, 1)));
+    HIP_TRY(sc.rows.reserve((size_t)std::max(nq, 1) * mr * 5));
+    HIP_TRY(sc.nrows.reserve((size_t)std::max(nq, 1)));
+    HIP_TRY(sc.votes.reserve((size_t)nq));
+    if (lds) HIP_TRY(sc.ranges.reserve((size_t)std::max<int64_t>(rec_cap, 1)));
     HIP_TRY(h.meta.reserve((size_t)3 * nq));
     if (lds) HIP_TRY(h.nrows.reserve((size_t)nq));
     if (lds && want_rows) HIP_TRY(h.rows.reserve((size_t)nq * mr * 5));
     int64_t *p_start = h.meta.p, *p_count = p_start + nq, *p_votes = p_count + nq;
     if (!have_starts) HIP_TRY(hipMemcpyAsync(p_start, qstart_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(p_count, qcount_dev, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    launch_query_votes(recs, qstart_dev, qcount_dev, nq, ix.offsets, e->q_votes.p, lds ? e->q_ranges.p : nullptr, s);
+    launch_query_votes(recs, qstart_dev, qcount_dev, nq, ix.offsets, sc.votes.p, lds ? sc.ranges.p : nullptr, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(p_votes, e->q_votes.p, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(p_votes, sc.votes.p, nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     if (!lds) return AID_OK;
     {
         ProfScope ps(e, AID_K_MATCH, s, true);
         launch_match_lds(recs, qstart_dev, qcount_dev, nq, ix.offsets, ix.post, ix.tomb, ix.n_tracks, e->cfg.min_match,
-                         mr, e->q_rows.p, e->q_nrows.p, ix.check_tomb, e->q_votes.p, ix.sig, e->q_ranges.p, s);
+                         mr, sc.rows.p, sc.nrows.p, ix.check_tomb, sc.votes.p, ix.sig, sc.ranges.p, s);
     }
     HIP_TRY(hipGetLastError());
     if (want_rows)
-        HIP_TRY(hipMemcpyAsync(h.rows.p, e->q_rows.p, (size_t)nq * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h.nrows.p, e->q_nrows.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.rows.p, sc.rows.p, (size_t)nq * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h.nrows.p, sc.nrows.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     return AID_OK;
 }
 
 // Phase 2, once the caller has waited for phase 1: the statistics of the nq queries (each counted here and nowhere
 // else), nrows[q] of the queries the LDS pass answered, and in `todo` the ones it handed back (all, without `lds`).
-static void k5_tally(aid_engine *e, const K5Host &h, int nq, bool lds, int32_t *nrows, std::vector<int> &todo) {
+// first_pass = false for the live index's delta pass: a query is counted once, its votes, records, reads and
+// hand-backs in every pass.
+static void k5_tally(aid_engine *e, const K5Host &h, int nq, bool lds, int32_t *nrows, std::vector<int> &todo,
+                     bool first_pass = true) {
     const int64_t *counts = h.meta.p + nq, *votes = counts + nq;
     todo.clear();
-    e->st_queries += nq;
+    if (first_pass) e->st_queries += nq;
     for (int q = 0; q < nq; ++q) {
         e->st_votes += votes[q];
         e->st_records += counts[q];
@@ -91,16 +95,16 @@ static void k5_tally(aid_engine *e, const K5Host &h, int nq, bool lds, int32_t *
     }
 }
 
-// Phase 3: the global-histogram path over the queries `todo` of a batch whose starts, counts and votes are on the
-// host, until each has its rows (rows + q * max_results, or with rows == nullptr its slot of e->q_rows) and
+// Phase 3: the global-histogram path, against the CSR segment `ix`, over the queries `todo` of a batch whose starts,
+// counts and votes are on the host, until each has its rows (rows + q * max_results, or with rows == nullptr its slot
+// of `dev_rows`, the pass's K5Scratch::rows) and
 // nrows[q]. Ends with the stream drained. vmax sizes the histogram and the key partitions: run_queries passes the
 // maximum over its whole batch, collect the maximum over the handed-back queries only (each as before the phases
 // were shared; making them one changes a fallback pass's histogram size, so its speed).
-static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start, const int64_t *h_count,
-                     const int64_t *h_votes, int64_t vmax, std::vector<int> todo, aid_match_row *rows, int32_t *nrows,
-                     hipStream_t s) {
+static int k5_global(aid_engine *e, const CsrView &ix, int32_t *dev_rows, const uint64_t *recs, const int64_t *h_start,
+                     const int64_t *h_count, const int64_t *h_votes, int64_t vmax, std::vector<int> todo,
+                     aid_match_row *rows, int32_t *nrows, hipStream_t s) {
     const int mr = e->cfg.max_results;
-    const CsrView ix = e->idx.view();
     const double votes = (double)vmax;
     const int parts = e->k5_parts > 0 ? e->k5_parts : votes > (double)(1 << 18) ? 2 : 1;
     const double m_seen = (double)(1 << 20), vp = votes / parts;
@@ -160,7 +164,7 @@ static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start
         } else {  // device mode: the batch's rows go to their queries' slots of q_rows
             HIP_TRY(e->x_order.reserve(order.size()));
             HIP_TRY(hipMemcpyAsync(e->x_order.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            launch_rows_scatter(out_rows, e->x_order.p, n, mr, e->q_rows.p, s);
+            launch_rows_scatter(out_rows, e->x_order.p, n, mr, dev_rows, s);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(got_n.data(), out_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -180,21 +184,64 @@ static int k5_global(aid_engine *e, const uint64_t *recs, const int64_t *h_start
     return AID_OK;
 }
 
-// K5 over nq queries, synchronously. rows == nullptr: device mode, every query's rows end in e->q_rows
-// ([nq][max_results][5] int32); nrows (host) is always filled
+// K5 over nq queries, synchronously. rows == nullptr: device mode, every query's rows end in e->q.rows
+// ([nq][max_results][5] int32); nrows (host) is always filled. Over the live index (a delta that holds postings) both
+// segments' LDS passes are queued before the one wait, each segment resolves its own hand-backs, and every query's
+// two row lists are merged by merge_rows (aidfp_live_plan.h): on the host, or in device mode by k_rows_merge, so that
+// K8b reads final rows from e->q.rows. A query is final only when both segments have answered it.
 static int run_queries(aid_engine *e, const uint64_t *recs, const int64_t *qstart_dev, const int64_t *qcount_dev,
-                       int nq, int64_t rec_cap, aid_match_row *rows, int32_t *nrows, hipStream_t s) {
-    const bool lds = e->k5_path != 2;
-    K5Host &h = e->k5h;
-    if (int rc = k5_enqueue(e, recs, qstart_dev, qcount_dev, nq, rec_cap, lds, rows != nullptr, h, s)) return rc;
+                       int nq, int64_t rec_cap, aid_match_row *rows_out, int32_t *nrows, hipStream_t s) {
+    const bool lds = e->k5_path != 2, two = e->idx.delta_live();
+    const int mr = e->cfg.max_results;
+    // ROWS_MERGE force: a host-row call keeps its rows on the device as the lane does, and copies the merged rows out
+    aid_match_row *rows = two && e->rows_merge_dev ? nullptr : rows_out;
+    K5Host &h = e->k5h, &hd = e->k5h_d;
+    const CsrView vm = e->idx.view();
+    if (int rc = k5_enqueue(e, vm, e->q, recs, qstart_dev, qcount_dev, nq, rec_cap, lds, rows != nullptr, h, s)) return rc;
+    if (two)
+        if (int rc = k5_enqueue(e, e->idx.view(*e->idx.delta), e->qd, recs, qstart_dev, qcount_dev, nq, rec_cap, lds,
+                                rows != nullptr, hd, s))
+            return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    if (lds && rows) std::memcpy(rows, h.rows.p, (size_t)nq * e->cfg.max_results * sizeof(aid_match_row));
+    if (lds && rows) std::memcpy(rows, h.rows.p, (size_t)nq * mr * sizeof(aid_match_row));
     std::vector<int> todo;
     k5_tally(e, h, nq, lds, nrows, todo);
     const int64_t *h_start = h.meta.p, *h_count = h_start + nq, *h_votes = h_count + nq;
     int64_t vmax = 1;
     for (int q = 0; q < nq; ++q) vmax = std::max(vmax, h_votes[q]);
-    return k5_global(e, recs, h_start, h_count, h_votes, vmax, std::move(todo), rows, nrows, s);
+    if (int rc = k5_global(e, vm, e->q.rows.p, recs, h_start, h_count, h_votes, vmax, std::move(todo), rows, nrows, s))
+        return rc;
+    if (!two) return AID_OK;
+    // the delta pass's hand-backs against the delta's own view, then the merge
+    std::vector<aid_match_row> rows_d(rows ? (size_t)nq * mr : 0);
+    std::vector<int32_t> nrows_d((size_t)nq, 0);
+    if (lds && rows) std::memcpy(rows_d.data(), hd.rows.p, (size_t)nq * mr * sizeof(aid_match_row));
+    k5_tally(e, hd, nq, lds, nrows_d.data(), todo, false);
+    const int64_t *d_start = hd.meta.p, *d_count = d_start + nq, *d_votes = d_count + nq;
+    vmax = 1;
+    for (int q = 0; q < nq; ++q) vmax = std::max(vmax, d_votes[q]);
+    if (int rc = k5_global(e, e->idx.view(*e->idx.delta), e->qd.rows.p, recs, d_start, d_count, d_votes, vmax,
+                           std::move(todo), rows ? rows_d.data() : nullptr, nrows_d.data(), s))
+        return rc;
+    if (rows) {
+        for (int q = 0; q < nq; ++q)
+            nrows[q] = merge_rows(reinterpret_cast<int32_t *>(rows + (size_t)q * mr), nrows[q],
+                                  reinterpret_cast<const int32_t *>(rows_d.data() + (size_t)q * mr), nrows_d[q], mr);
+        return AID_OK;
+    }
+    // device mode: both passes' final counts go up (the LDS pass left -reason where it handed a query back)
+    HIP_TRY(hipMemcpyAsync(e->q.nrows.p, nrows, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->qd.nrows.p, nrows_d.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(e, AID_K_ROWS_MERGE, s, true);
+        launch_rows_merge(e->q.rows.p, e->q.nrows.p, e->qd.rows.p, e->qd.nrows.p, nq, mr, s);
+    }
+    HIP_TRY(hipGetLastError());
+    if (rows_out)
+        HIP_TRY(hipMemcpyAsync(rows_out, e->q.rows.p, (size_t)nq * mr * sizeof(aid_match_row), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // nrows and nrows_d are pageable: their copies must not outlive this call
+    for (int q = 0; q < nq; ++q) nrows[q] = std::min(std::max(nrows[q], 0) + std::max(nrows_d[q], 0), mr);
+    return AID_OK;
 }
 
 // K5 keys its distinct-frame sets by (table slot << 20 | t_q) (index.hip distinct_first): a query's anchor frames must
@@ -304,6 +351,9 @@ static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64
                          int32_t n, int32_t loc, void *stream, aid_query_ticket *t) {
     t->nq = n;
     t->nrec = 0;
+    t->two = false;
+    t->seg_main.reset();  // (a pooled ticket that went back without a collect)
+    t->seg_delta.reset();
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = ensure_index(e)) return rc;
     if (n == 0) return AID_OK;
@@ -322,7 +372,23 @@ static int submit_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64
     HIP_TRY(hipMemcpyAsync(t->qsc.p + nq, e->ext.counts.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(t->recs.p, e->ext.records.p, (size_t)t->nrec * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     // always the LDS pass: a ticket ignores the K5_PATH force (collect runs the global path for what it hands back)
-    if (int rc = k5_enqueue(e, t->recs.p, t->qsc.p, t->qsc.p + nq, nq, t->nrec, true, true, t->host, s, true)) return rc;
+    if (int rc = k5_enqueue(e, e->idx.view(), e->q, t->recs.p, t->qsc.p, t->qsc.p + nq, nq, t->nrec, true, true, t->host,
+                            s, true))
+        return rc;
+    // live index: the delta's LDS pass behind main's, into the ticket's second result block; the ticket holds both
+    // segments, so collect resolves each one's hand-backs against the views it was submitted under
+    t->two = e->idx.delta_live();
+    if (e->idx.live_cap > 0) {
+        t->seg_main = e->idx.main;
+        t->seg_delta = t->two ? e->idx.delta : nullptr;
+    }
+    if (t->two) {
+        HIP_TRY(t->host_d.meta.reserve((size_t)3 * nq));
+        std::memcpy(t->host_d.meta.p, t->host.meta.p, (size_t)nq * sizeof(int64_t));
+        if (int rc = k5_enqueue(e, e->idx.view(*e->idx.delta), e->qd, t->recs.p, t->qsc.p, t->qsc.p + nq, nq, t->nrec, true,
+                                true, t->host_d, s, true))
+            return rc;
+    }
     HIP_TRY(t->ev.record(s));
     return AID_OK;
 }
@@ -399,14 +465,24 @@ extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid
     struct Back {  // back to the pool on every return below (the ticket's work has completed)
         aid_engine *e;
         aid_query_ticket *t;
-        ~Back() { e->ticket_pool.emplace_back(t); }
+        ~Back() {
+            t->seg_main.reset();  // the segments it held go back to the index (or, replaced meanwhile, are freed)
+            t->seg_delta.reset();
+            e->ticket_pool.emplace_back(t);
+        }
     } back{e, t};
     if (t->nq == 0) return AID_OK;
     const int nq = t->nq, mr = e->cfg.max_results;
     std::memcpy(rows, t->host.rows.p, (size_t)nq * mr * sizeof(aid_match_row));
+    // the views the ticket was submitted under where it holds its segments (live index), else the index's own. The
+    // track table is the engine's current one either way; a held segment that a build has replaced meanwhile checks
+    // it for every posting (removals since then were counted on its successor)
+    const HashIndex &hx = e->idx;
+    CsrView vm = t->seg_main ? hx.view(*t->seg_main) : hx.view();
+    if (t->seg_main && t->seg_main != hx.main) vm.check_tomb = 1;
     std::vector<int> todo;
     k5_tally(e, t->host, nq, true, nrows, todo);
-    if (todo.empty()) return AID_OK;
+    if (todo.empty() && !t->two) return AID_OK;
     // the queries the LDS pass handed back: the global path over the ticket's own copy of their records. It uses
     // engine-wide scratch, which the K5 of a later submit on another stream may still be using
     HIP_TRY(hipSetDevice(e->device));
@@ -414,7 +490,27 @@ extern "C" int aid_query_windows_collect(aid_engine *e, aid_query_ticket *t, aid
     const int64_t *starts = t->host.meta.p, *counts = starts + nq, *votes = counts + nq;
     int64_t vmax = 1;
     for (int q : todo) vmax = std::max(vmax, votes[q]);
-    return k5_global(e, t->recs.p, starts, counts, votes, vmax, std::move(todo), rows, nrows, t->s);
+    if (!todo.empty())
+        if (int rc = k5_global(e, vm, nullptr, t->recs.p, starts, counts, votes, vmax, std::move(todo), rows, nrows, t->s))
+            return rc;
+    if (!t->two) return AID_OK;
+    CsrView vd = hx.view(*t->seg_delta);
+    if (t->seg_delta != hx.delta) vd.check_tomb = 1;
+    std::vector<aid_match_row> rows_d((size_t)nq * mr);
+    std::vector<int32_t> nrows_d((size_t)nq, 0);
+    std::memcpy(rows_d.data(), t->host_d.rows.p, (size_t)nq * mr * sizeof(aid_match_row));
+    k5_tally(e, t->host_d, nq, true, nrows_d.data(), todo, false);
+    const int64_t *d_votes = t->host_d.meta.p + 2 * (size_t)nq;
+    vmax = 1;
+    for (int q : todo) vmax = std::max(vmax, d_votes[q]);
+    if (!todo.empty())
+        if (int rc = k5_global(e, vd, nullptr, t->recs.p, starts, counts, d_votes, vmax, std::move(todo), rows_d.data(),
+                               nrows_d.data(), t->s))
+            return rc;
+    for (int q = 0; q < nq; ++q)
+        nrows[q] = merge_rows(reinterpret_cast<int32_t *>(rows + (size_t)q * mr), nrows[q],
+                              reinterpret_cast<const int32_t *>(rows_d.data() + (size_t)q * mr), nrows_d[q], mr);
+    return AID_OK;
 }
 
 static int query_windows_entry(const char *fn, aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *starts,
@@ -572,15 +668,15 @@ int exact_lane_device(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t 
         if (int rc = run_queries(e, e->ext.records.p, e->q_start.p, e->ext.counts.p, n_win,
                                  (int64_t)e->ext.records.n, nullptr, nrows.data(), s))
             return rc;
-        HIP_TRY(e->q_nrows.reserve((size_t)n_win));
-        HIP_TRY(hipMemcpyAsync(e->q_nrows.p, nrows.data(), n_win * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(e->q.nrows.reserve((size_t)n_win));
+        HIP_TRY(hipMemcpyAsync(e->q.nrows.p, nrows.data(), n_win * sizeof(int32_t), hipMemcpyHostToDevice, s));
     } else {
-        HIP_TRY(e->q_nrows.reserve(1));
-        HIP_TRY(e->q_rows.reserve((size_t)mr * 5));
-        HIP_TRY(hipMemsetAsync(e->q_nrows.p, 0, sizeof(int32_t), s));
+        HIP_TRY(e->q.nrows.reserve(1));
+        HIP_TRY(e->q.rows.reserve((size_t)mr * 5));
+        HIP_TRY(hipMemsetAsync(e->q.nrows.p, 0, sizeof(int32_t), s));
     }
     const double sec = (double)e->cfg.hop / (double)e->cfg.sample_rate;
-    launch_exact_consensus(e->q_rows.p, e->q_nrows.p, mr, e->x_clipwin.p, n_clips, sec, max_out, e->x_out.p, e->x_nout.p,
+    launch_exact_consensus(e->q.rows.p, e->q.nrows.p, mr, e->x_clipwin.p, n_clips, sec, max_out, e->x_out.p, e->x_nout.p,
                            s);
     HIP_TRY(hipGetLastError());
     return AID_OK;

@@ -57,7 +57,9 @@ extern "C" {
 #define AID_K_VOTE_FINAL 11  /* K5b: exact (track, d) table of the hot votes, best d per track, rows */
 #define AID_K_RESAMPLE_SPEEDS 12 /* K6s: every speed variant of a clip group, one launch */
 #define AID_K_SPEED_SELECT 13    /* K8c: per-clip speed selection over the lane's rows */
-#define AID_K_COUNT 14       /* AID_K_MATCH (5) is the LDS match path (k_match_lds) */
+#define AID_K_ROWS_MERGE 14      /* live index: a query's rows from the two CSR segments merged (device-row callers) */
+#define AID_K_INDEX_MERGE 15     /* K4m: the live index's delta folded into main (offsets, tile totals, merge) */
+#define AID_K_COUNT 16       /* AID_K_MATCH (5) is the LDS match path (k_match_lds) */
 
 typedef struct aid_engine aid_engine;
 
@@ -121,6 +123,9 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
                                       and keys per selection slice (tests: a small catalog spans several chunks) */
 #define AID_FORCE_SPEED_GROUP 12   /* 0 default (2^28: 1 GiB), else variant samples per clip group of one
                                       aid_exact_lane_speeds call (tests: a small call split into several groups) */
+#define AID_FORCE_ROWS_MERGE 13    /* live index: 0 default (the host-row query calls merge a query's two row lists on the
+                                      host), 1: they merge on the device (k_rows_merge, as aid_exact_lane always
+                                      does) and copy the merged rows out (tests: constructed lists through the kernel) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
@@ -233,7 +238,41 @@ int aid_index_remove(aid_engine *e, uint32_t track);
 /* Drop the stored postings of every removed track (order of the others kept; the LMDB delete of
  * `olaf_c del` frees its entries). *n_removed = postings dropped. The CSR is rebuilt lazily. */
 int aid_index_compact(aid_engine *e, int64_t *n_removed);
+/* One CSR over every stored posting, built now. With the live index on (below) it folds the delta segment into main,
+   or runs the full build if a track was removed since main's build; aid_index_csr_export then sees everything. */
 int aid_index_finalize(aid_engine *e);
+/* ---- ingest while serving: the live index (two CSR segments) ----
+ * Off (the default), any stored posting makes the next query rebuild the whole CSR. On, the CSR built last stays as
+ * the MAIN segment and the postings stored since go into a second, small CSR, the DELTA, which alone is rebuilt
+ * (O(delta + 2^26)); every query votes over both segments and its rows are merged: match_count descending, then
+ * track id ascending, cut at max_results. When the delta would pass max_delta_postings it is FOLDED into main: the
+ * two CSRs share the bucket order, so K4m merges them in one streaming pass, without a sort. A fold carries the
+ * postings of tracks removed since main's build along (queries keep skipping them); the next full build drops them. Results do not depend on the segmentation (FPSPEC 7): a row's score is per (track, d), and
+ * the rule below keeps every track's postings in one segment.
+ * Rules:
+ *  - Disjointness: an append keeps main only if every track id it carries is >= the track count (max id + 1) at
+ *    main's build. An append with an older id, and aid_index_compact, _reset, _load, _splice / _allgather and a
+ *    K4_BUILD force, fall back to the full build at the next query and empty the delta (counted by reason).
+ *  - aid_index_remove works as ever: both segments skip the track's postings from then on.
+ *  - aid_index_save / _load / _export / _checksum and the exchange read the stored postings and do not see segments.
+ *    aid_index_csr_export fails with AID_ERR_STATE while postings sit in the delta; aid_index_finalize first.
+ *  - aid_index_stats' n_live is the sum over both segments (-1 while stored postings wait for their build).
+ *  - Tickets: a ticket submitted with the feature on holds the CSR segments it was submitted under until it is
+ *    collected, and collect answers its handed-back queries against those. A store, delta rebuild or fold between
+ *    submit and collect therefore never frees or overwrites what the ticket reads: the build that finds a segment held
+ *    builds into new buffers, and the held ones are freed at collect. An uncollected ticket can so keep one extra copy
+ *    of a segment alive (8 + 2 B per posting and the 256 MB offset array): collect tickets promptly. Its rows are those
+ *    of the index as it was at submit, except that tracks removed since may be missing from handed-back queries.
+ * aid_index_live: max_delta_postings = 0 turns the feature off, > 0 on with that cap. A change while a delta holds
+ * postings folds first. */
+int aid_index_live(aid_engine *e, int64_t max_delta_postings);
+/* The first n of 13 counters since the engine was created: out[0] full (K4) builds of main, [1] delta builds (a fold
+   first builds the delta over the whole tail, and counts here), [2] folds (K4m merges of the delta into main),
+   [3] postings in main, [4] postings stored since (the delta's), [5] the
+   track count at main's last build, [6..12] fall-backs from a valid main to the full build while the feature was on,
+   by reason: an append with an older track id, aid_index_compact, _reset, _load, a splice / all-gather, a K4_BUILD
+   force, aid_index_finalize with a track removed since main's build. */
+int aid_index_live_stats(aid_engine *e, int64_t *out, int32_t n);
 /* Cumulative match counters since the last reset (the first n of 7): out[0] queries, [1] exact votes (postings whose
    hash a query record hits), [2] 8-B postings K5's global path read (once per key partition in K5a + once in K5b),
    [3] queries answered on the LDS path, [4] on the global path, [5] query records, [6] 2-B posting signatures the
@@ -241,7 +280,9 @@ int aid_index_finalize(aid_engine *e);
    vote whose bucket is hot), [7] resident LDS-path workgroups per CU (an occupancy query, not a counter),
    [8..12] queries the LDS path handed to the global path, by reason: above 2^18 votes, (track, d) table full,
    distinct-frame set full, track table full, more rows than its staging holds. Not counters either: [13] the K2
-   width (AID_FORCE_K2_WIDTH) and [14] the K2 strips of the engine's last extraction call. */
+   width (AID_FORCE_K2_WIDTH) and [14] the K2 strips of the engine's last extraction call. Over the live index
+   (aid_index_live) a query runs one pass per CSR segment: it is counted once in [0], while votes, records, reads,
+   the LDS / global path counts [3] [4] and the hand-backs are summed over its passes. */
 int aid_match_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
 /* n_postings = stored postings, n_live = postings in the built CSR (-1 if stale), n_tracks = max id + 1 */
 int aid_index_stats(aid_engine *e, int64_t *n_postings, int64_t *n_live, uint32_t *n_tracks);
