@@ -302,7 +302,7 @@ class Engine:
              "k2_strips_x100": L.AID_FORCE_K2_STRIPS_X100, "k4_build": L.AID_FORCE_K4_BUILD,
              "exchange_fail": L.AID_FORCE_EXCHANGE_FAIL, "lane_gather": L.AID_FORCE_LANE_GATHER,
              "plane_rows": L.AID_FORCE_PLANE_ROWS, "k2_width": L.AID_FORCE_K2_WIDTH,
-             "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK,
+             "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK, "vec_cand": L.AID_FORCE_VEC_CAND,
              "speed_group": L.AID_FORCE_SPEED_GROUP, "rows_merge": L.AID_FORCE_ROWS_MERGE}
 
     def force(self, what: str, value: int) -> None:

@@ -11,6 +11,7 @@
 
 #include "../../include/aidfp.h"
 #include "aidfp_buffers.h"
+#include "aidfp_vector_q8.h"
 
 namespace aid {
 
@@ -47,6 +48,23 @@ struct VecCatalog {
     // aid_vec_stats, in its order: batches by threshold, not eligible, overflowed; slice-route select launches;
     // largest candidate count; reallocations that copied rows; MFMA and VALU scan launches
     int64_t st[kVecStats] = {};
+    // int8 prefilter (FPSPEC 9.1), off by default. While it is on, the planes below mirror rows [0, n) of d_vecs:
+    // int8 rows in the layout of aidfp_vector_q8.h, their scales s and residuals e (both also on the host), and E =
+    // the largest e. q8_rows = the rows the planes were built for (cap_rows, or 0 = not built)
+    int q8_mode = 0;      // aid_vec_prefilter: 0 off, 1 int8
+    int q8_over = 4;      // oversample
+    int force_cand = 0;   // AID_FORCE_VEC_CAND
+    int64_t q8_rows = 0;
+    float q8_E = 0.0f;
+    DevBuf<int8_t, 64> d_v8;
+    DevBuf<float, 64> d_s8, d_e8;
+    std::vector<float> h_s8, h_e8;
+    // aid_vec_prefilter_stats, in its order: queries answered by the prefilter, queries that fell back to the f32
+    // scan, total |W|, largest |W|, rescored pairs, int8 scan launches
+    int64_t q8st[kVecQ8Stats] = {};
+    DevBuf<int8_t, 64> d_q8;
+    DevBuf<float, 64> d_qs, d_qe, d_fbq;
+    DevBuf<int32_t, 64> d_qmap;
     // scratch
     DevBuf<float, 64> d_raw, d_q, d_scores;
     DevBuf<unsigned long long, 64> d_keys0, d_keys1, d_cand;
@@ -74,7 +92,22 @@ int vec_aggregate(VecCatalog &c, const aid_vec_hit *hits, const int64_t *hoff, i
                   hipStream_t s);
 int vec_lane(VecCatalog &c, const float *queries, int nq, int location, int limit, int top_k, double weight,
              const uint32_t *exclude, double threshold, int max_out, aid_vibe_row *out, int32_t *n_out, hipStream_t s);
+int vec_prefilter(VecCatalog &c, int mode, int oversample, hipStream_t s);
+int vec_scores_i8(VecCatalog &c, const float *queries, int nq, int location, float *approx_out, double *eps_out,
+                  int64_t cap, hipStream_t s);
 int vec_save(VecCatalog &c, const char *path, hipStream_t s);
 int vec_load(VecCatalog &c, const char *path, hipStream_t s);
+
+// launches of csrc/vector_q8.hip (K9q); the caller checks hipGetLastError (vec_q8_rescore returns it)
+void vec_q8_quantize(const float *tiled, int64_t row0, int64_t n, int dim, int8_t *dst, float *s_out, float *e_out,
+                     hipStream_t s);
+void vec_q8_scan(const int8_t *cat, const float *cat_s, int64_t n_tiles, int tiles_per_wg, const int8_t *q,
+                 const float *q_s, int nqt, int dim, float *scores, int64_t ns, hipStream_t s);
+hipError_t vec_q8_rescore(const float *cat, const float *q, int dim, unsigned long long *keys, int64_t stride, int n_max,
+                          const int32_t *cnt, int cnt_cap, int nb, hipStream_t s);
+void vec_q8_filter(const float *scores, int64_t ns, const uint8_t *dead, int64_t n, const uint32_t *thr,
+                   unsigned long long *cand, int cap, int32_t *cnt, int nb, hipStream_t s);
+void vec_q8_tau(const unsigned long long *keys, int64_t stride, int R, int limit, const float *q_e, float E, int dim,
+                uint32_t *thr, int32_t *cnt, int nb, hipStream_t s);
 
 }  // namespace aid

@@ -206,6 +206,10 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
                 return fail(AID_ERR_INVALID, "VEC_CHUNK: 0 default, else a multiple of 32 in [32, 4096]");
             e->vec.force_chunk = value;
             return AID_OK;
+        case AID_FORCE_VEC_CAND:
+            if (value < 0 || value > kVecCandCap) return fail(AID_ERR_INVALID, "VEC_CAND: 0 default, else in [1, 4096]");
+            e->vec.force_cand = value;
+            return AID_OK;
         case AID_FORCE_SPEED_GROUP:
             if (value < 0) return fail(AID_ERR_INVALID, "SPEED_GROUP must be >= 0");
             e->speed_group = value;
@@ -599,6 +603,24 @@ int aid_vec_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
     for (int i = 0; i < n && i < kVecStats; ++i) out[i] = e->vec.st[i];
     if (reset)
         for (auto &v : e->vec.st) v = 0;
+    return AID_OK;
+}
+
+int aid_vec_prefilter(aid_engine *e, int32_t mode, int32_t oversample) {
+    VEC_CALL(e, nullptr, vec_prefilter(e->vec, mode, oversample, s));
+}
+
+int aid_vec_scores_i8(aid_engine *e, const float *queries, int32_t nq, int32_t location, float *approx_out,
+                      double *eps_out, int64_t cap) {
+    VEC_CALL(e, nullptr, vec_scores_i8(e->vec, queries, nq, location, approx_out, eps_out, cap, s));
+}
+
+int aid_vec_prefilter_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset) {
+    if (!e || (n > 0 && !out)) return fail(AID_ERR_INVALID, "aid_vec_prefilter_stats: bad argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (int i = 0; i < n && i < kVecQ8Stats; ++i) out[i] = e->vec.q8st[i];
+    if (reset)
+        for (auto &v : e->vec.q8st) v = 0;
     return AID_OK;
 }
 

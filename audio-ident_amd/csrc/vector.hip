@@ -15,6 +15,9 @@
 //                     where the threshold route does not apply (fewer slices than `limit`, or too many ties)
 //   k_vec_hits        final keys -> hit columns
 //   k_vec_aggregate   one wave per query, binary64, in LDS
+//
+// The opt-in int8 prefilter (FPSPEC 9.1, aid_vec_prefilter) answers the same searches from an int8 copy of the
+// catalog plus exact rescoring; its kernels are in csrc/vector_q8.hip, its host route (vec_search_q8) is here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -23,6 +26,7 @@
 #include <algorithm>
 
 #include "aidfp_vector.h"
+#include "aidfp_vector_keys.h"
 
 namespace aid {
 
@@ -153,41 +157,6 @@ __global__ __launch_bounds__(256) void k_vec_scan_valu(const float *__restrict__
     scores[(size_t)qi * ns + e] = acc;
 }
 
-// Selection keys: larger = better. vec_score_key maps a score's bits so that unsigned order is numeric order
-// (-0 counts as +0; never 0 for a number). The 64-bit key has it in the high word and ~entry in the low word, so
-// the lower entry wins a tie. 0 = no entry.
-__device__ __forceinline__ uint32_t vec_score_key(float score) {
-    uint32_t b = __float_as_uint(score);
-    if (b == 0x80000000u) b = 0;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long vec_key(float score, uint32_t entry) {
-    return ((unsigned long long)vec_score_key(score) << 32) | (0xFFFFFFFFu - entry);
-}
-__device__ __forceinline__ float vec_key_score(unsigned long long key) {
-    const uint32_t m = (uint32_t)(key >> 32);
-    return __uint_as_float((m & 0x80000000u) ? (m & 0x7FFFFFFFu) : ~m);
-}
-
-// Bitonic sort, descending, of sp (a power of two) keys in LDS by a 256-thread workgroup.
-template <typename T>
-__device__ __forceinline__ void vec_sort_desc(T *keys, int sp) {
-    for (int k = 2; k <= sp; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (sp >> 1); t += 256) {
-                const int i = 2 * t - (t & (j - 1));
-                const T a = keys[i], b = keys[i + j];
-                const bool desc = (i & k) == 0;
-                if ((a < b) == desc && a != b) {
-                    keys[i] = b;
-                    keys[i + j] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // Slice blockIdx.x of query blockIdx.y: keys of `slice` inputs (scores of live entries on the first pass, the
 // previous pass's keys after it) sorted descending in LDS; the first `keep` go to out[q][slice_index][keep].
 __global__ __launch_bounds__(256) void k_vec_select(const float *__restrict__ scores, int64_t ns,
@@ -273,14 +242,17 @@ __global__ __launch_bounds__(256) void k_vec_filter(const float *__restrict__ sc
     }
 }
 
-// Final keys of query blockIdx.x (a sorted prefix of non-zero keys among `have`) -> hit columns [q][limit].
+// Final keys of query blockIdx.x (a sorted prefix of non-zero keys among `have`) -> hit columns [q][limit]. With
+// qmap the columns of query blockIdx.x are those of qmap[blockIdx.x] (the prefilter's fallback queries, which are
+// scanned as a tile of their own).
 __global__ __launch_bounds__(256) void k_vec_hits(const unsigned long long *__restrict__ keys, int64_t stride, int have,
                                                   int limit, const uint32_t *__restrict__ track,
-                                                  const double *__restrict__ off, uint32_t *__restrict__ h_entry,
-                                                  uint32_t *__restrict__ h_track, float *__restrict__ h_score,
-                                                  double *__restrict__ h_off, int32_t *__restrict__ n_hits) {
-    const int q = blockIdx.x;
-    const unsigned long long *k = keys + (size_t)q * stride;
+                                                  const double *__restrict__ off, const int32_t *__restrict__ qmap,
+                                                  uint32_t *__restrict__ h_entry, uint32_t *__restrict__ h_track,
+                                                  float *__restrict__ h_score, double *__restrict__ h_off,
+                                                  int32_t *__restrict__ n_hits) {
+    const unsigned long long *k = keys + (size_t)blockIdx.x * stride;
+    const int q = qmap ? qmap[blockIdx.x] : (int)blockIdx.x;
     if (threadIdx.x == 0 && (have == 0 || k[0] == 0)) n_hits[q] = 0;
     for (int i = threadIdx.x; i < have; i += 256) {
         const unsigned long long key = k[i];
@@ -424,14 +396,88 @@ static int vfail(VecCatalog &c, int code, const std::string &msg) {
 
 static bool vec_dim_ok(int dim) { return dim >= 32 && dim <= 1024 && dim % 32 == 0; }
 
+// ---- the int8 planes of the prefilter (FPSPEC 9.1): a pure function of the stored f32 rows
+static void vec_q8_release(VecCatalog &c) {
+    c.d_v8.release();
+    c.d_s8.release();
+    c.d_e8.release();
+    c.h_s8.clear();
+    c.h_e8.clear();
+    c.q8_rows = 0;
+    c.q8_E = 0.0f;
+}
+
+// Quantise rows [row0, row0 + n) of d_vecs into the planes, bring their s and e to the host mirror (whose size is
+// row0 on entry) and fold them into E.
+static int vec_q8_append(VecCatalog &c, int64_t row0, int64_t n, hipStream_t s) {
+    if (n <= 0) return AID_OK;
+    vec_q8_quantize(c.d_vecs.p, row0, n, c.dim, c.d_v8.p, c.d_s8.p, c.d_e8.p, s);
+    VEC_TRY(hipGetLastError());
+    c.h_s8.resize((size_t)(row0 + n));
+    c.h_e8.resize((size_t)(row0 + n));
+    VEC_TRY(hipMemcpyAsync(c.h_s8.data() + row0, c.d_s8.p + row0, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    VEC_TRY(hipMemcpyAsync(c.h_e8.data() + row0, c.d_e8.p + row0, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    VEC_TRY(hipStreamSynchronize(s));
+    for (int64_t i = row0; i < row0 + n; ++i) c.q8_E = std::max(c.q8_E, c.h_e8[i]);
+    return AID_OK;
+}
+
+// Build the planes for the catalog as it stands (cap_rows rows, the first n quantised, the rest zero): on enabling,
+// after a load, and when the f32 block has grown.
+static int vec_q8_rebuild(VecCatalog &c, hipStream_t s) {
+    c.h_s8.clear();
+    c.h_e8.clear();
+    c.q8_E = 0.0f;
+    c.q8_rows = 0;
+    if (!c.cap_rows) return AID_OK;
+    const size_t rows = (size_t)c.cap_rows;
+    VEC_TRY(c.d_v8.reserve(rows * c.dim));
+    VEC_TRY(c.d_s8.reserve(rows));
+    VEC_TRY(c.d_e8.reserve(rows));
+    VEC_TRY(hipMemsetAsync(c.d_v8.p, 0, rows * c.dim, s));
+    VEC_TRY(hipMemsetAsync(c.d_s8.p, 0, rows * sizeof(float), s));
+    VEC_TRY(hipMemsetAsync(c.d_e8.p, 0, rows * sizeof(float), s));
+    c.q8_rows = c.cap_rows;
+    return vec_q8_append(c, 0, c.n, s);
+}
+
+int vec_prefilter(VecCatalog &c, int mode, int oversample, hipStream_t s) {
+    if ((mode != 0 && mode != 1) || oversample < 1 || oversample > kVecQ8MaxOversample)
+        return vfail(c, AID_ERR_INVALID, "aid_vec_prefilter: mode is 0 (off) or 1 (int8), oversample in [1, 64]");
+    c.q8_over = oversample;
+    if (mode == 0) {
+        if (c.q8_mode) (void)hipDeviceSynchronize();
+        c.q8_mode = 0;
+        vec_q8_release(c);
+        return AID_OK;
+    }
+    if (c.q8_mode == 1) return AID_OK;
+    c.q8_mode = 1;
+    if (int rc = vec_q8_rebuild(c, s)) {
+        c.q8_mode = 0;
+        vec_q8_release(c);
+        return rc;
+    }
+    return AID_OK;
+}
+
 int vec_reset(VecCatalog &c, int dim) {
     if (!vec_dim_ok(dim)) return vfail(c, AID_ERR_INVALID, "aid_vec_reset: dim must be a multiple of 32 in [32, 1024]");
     if (dim != c.dim && c.d_vecs.p) {  // another row size: the stored tiles are of no use
         (void)hipDeviceSynchronize();
         c.d_vecs.release();
         c.cap_rows = 0;
+        vec_q8_release(c);
     }
     if (c.d_vecs.p) VEC_TRY(hipMemset(c.d_vecs.p, 0, (size_t)c.cap_rows * dim * sizeof(float)));
+    if (c.q8_rows) {  // the int8 planes of an empty catalog: zero, as the f32 rows are
+        VEC_TRY(hipMemset(c.d_v8.p, 0, (size_t)c.q8_rows * dim));
+        VEC_TRY(hipMemset(c.d_s8.p, 0, (size_t)c.q8_rows * sizeof(float)));
+        VEC_TRY(hipMemset(c.d_e8.p, 0, (size_t)c.q8_rows * sizeof(float)));
+    }
+    c.h_s8.clear();
+    c.h_e8.clear();
+    c.q8_E = 0.0f;
     c.dim = dim;
     c.n = c.n_live = 0;
     c.h_track.clear();
@@ -482,6 +528,8 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
     if (n == 0) return AID_OK;
     if (c.n + n >= 0xFFFFFFFFll) return vfail(c, AID_ERR_INVALID, "aid_vec_add: more than 2^32 - 2 entries");
     if (int rc = vec_grow(c, c.n + n, s)) return rc;
+    if (c.q8_mode && c.q8_rows != c.cap_rows)  // the f32 block is new or has grown: so do the int8 planes
+        if (int rc = vec_q8_rebuild(c, s)) return rc;
     // payload to the host mirror first (a device caller's columns come back once; they are 16 bytes an entry)
     std::vector<uint32_t> tr(n);
     std::vector<int32_t> ch(n);
@@ -512,6 +560,8 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
     VEC_TRY(hipMemcpyAsync(c.d_off.p + c.n, of.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
     VEC_TRY(hipMemsetAsync(c.d_dead.p + c.n, 0, n, s));
     VEC_TRY(hipStreamSynchronize(s));
+    if (c.q8_mode)
+        if (int rc = vec_q8_append(c, c.n, n, s)) return rc;
     c.h_track.insert(c.h_track.end(), tr.begin(), tr.end());
     c.h_chunk.insert(c.h_chunk.end(), ch.begin(), ch.end());
     c.h_off.insert(c.h_off.end(), of.begin(), of.end());
@@ -556,6 +606,34 @@ int vec_compact(VecCatalog &c, int64_t *n_removed, hipStream_t s) {
         VEC_TRY(hipGetLastError());
         VEC_TRY(hipStreamSynchronize(s));
         std::swap(c.d_vecs, nb);
+    }
+    if (c.q8_mode && c.q8_rows) {
+        // the int8 rows move as the f32 rows do: a tile is [dim / 16][32] 16-byte units, which k_vec_gather copies
+        // bit for bit as the float4 units of a catalog of dim / 4
+        DevBuf<int8_t, 64> nb;
+        VEC_TRY(nb.reserve((size_t)c.q8_rows * c.dim));
+        const int64_t u16 = c.q8_rows * (c.dim / 16);
+        hipLaunchKernelGGL(k_vec_gather, dim3((unsigned)((u16 + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<const float4 *>(c.d_v8.p), c.d_hentry.p, m, c.q8_rows, c.dim / 4,
+                           reinterpret_cast<float4 *>(nb.p));
+        VEC_TRY(hipGetLastError());
+        VEC_TRY(hipStreamSynchronize(s));
+        std::swap(c.d_v8, nb);
+        c.q8_E = 0.0f;
+        for (int64_t r = 0; r < m; ++r) {
+            c.h_s8[r] = c.h_s8[map[r]];
+            c.h_e8[r] = c.h_e8[map[r]];
+            c.q8_E = std::max(c.q8_E, c.h_e8[r]);
+        }
+        c.h_s8.resize(m);
+        c.h_e8.resize(m);
+        VEC_TRY(hipMemsetAsync(c.d_s8.p, 0, (size_t)c.q8_rows * sizeof(float), s));
+        VEC_TRY(hipMemsetAsync(c.d_e8.p, 0, (size_t)c.q8_rows * sizeof(float), s));
+        if (m) {
+            VEC_TRY(hipMemcpyAsync(c.d_s8.p, c.h_s8.data(), m * sizeof(float), hipMemcpyHostToDevice, s));
+            VEC_TRY(hipMemcpyAsync(c.d_e8.p, c.h_e8.data(), m * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        VEC_TRY(hipStreamSynchronize(s));
     }
     for (int64_t r = 0; r < m; ++r) {
         c.h_track[r] = c.h_track[map[r]];
@@ -632,6 +710,216 @@ static int vec_stage_queries(VecCatalog &c, const float *queries, int nq, int lo
     return AID_OK;
 }
 
+// How one batch's hit lists are selected from its score matrix, for one `limit`.
+struct VecSelPlan {
+    int limit, slice, keep, mslice;
+    int64_t msl;
+    bool by_threshold;
+    bool q8 = false;  // the prefilter's selection over approx: candidate counts in lines of their own (k_vec_filter_q8)
+};
+
+// The plan for `limit`, with the scratch it needs.
+static int vec_sel_plan(VecCatalog &c, int limit, VecSelPlan &p) {
+    p.limit = limit;
+    // slice-by-slice route: a slice holds at least 2 * limit keys, so every pass shrinks the candidate set
+    p.slice = std::max(c.force_chunk ? c.force_chunk : kVecSelectSlice, 2 * pow2_ceil(limit));
+    p.keep = std::min(limit, p.slice);
+    const int64_t nsl0 = (c.n + p.slice - 1) / p.slice;
+    VEC_TRY(c.d_keys0.reserve((size_t)kVecQueryBatch * nsl0 * p.keep));
+    VEC_TRY(c.d_keys1.reserve((size_t)kVecQueryBatch * ((nsl0 * p.keep + p.slice - 1) / p.slice) * p.keep));
+    // threshold route: needs at least `limit` slices, and few enough of them for one sort of their maxima
+    p.mslice = c.force_chunk ? c.force_chunk
+                             : std::max(kVecMaxSlice, pow2_ceil((int)((c.n + kVecCandCap - 1) / kVecCandCap)));
+    p.msl = (c.n + p.mslice - 1) / p.mslice;
+    p.by_threshold = p.msl >= limit && p.msl <= kVecCandCap;
+    if (p.by_threshold) {
+        VEC_TRY(c.d_smax.reserve((size_t)kVecQueryBatch * p.msl));
+        VEC_TRY(c.d_thr.reserve((size_t)kVecQueryBatch));
+        VEC_TRY(c.d_ccnt.reserve((size_t)kVecQueryBatch));
+        VEC_TRY(c.d_cand.reserve((size_t)kVecQueryBatch * kVecCandCap));
+    }
+    return AID_OK;
+}
+
+// The best p.limit keys of each of the batch's nb rows of d_scores, sorted, at (*in)[q * *in_stride ..].
+static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, hipStream_t s, unsigned long long **in_out,
+                            int64_t *in_stride_out) {
+    const int64_t ns = (c.n + 31) / 32 * 32;
+    const int limit = p.limit, slice = p.slice, keep = p.keep, mslice = p.mslice;
+    const int64_t msl = p.msl;
+    unsigned long long *in = nullptr;
+    int64_t in_stride = 0;
+    if (p.by_threshold) {
+        int32_t cnt[kVecQueryBatch];
+        std::vector<int32_t> cnt_lines(p.q8 ? (size_t)nb * kVecQ8CntStride : 0);
+        hipLaunchKernelGGL(k_vec_slice_max, dim3((unsigned)msl, (unsigned)nb), dim3(256), 0, s, c.d_scores.p, ns,
+                           c.d_dead.p, c.n, mslice, (int)msl, c.d_smax.p);
+        const int msp = std::max(2, pow2_ceil((int)msl));
+        hipLaunchKernelGGL(k_vec_threshold, dim3((unsigned)nb), dim3(256), (size_t)msp * 4, s, c.d_smax.p, (int)msl, msp,
+                           limit, c.d_thr.p, c.d_ccnt.p);
+        VEC_TRY(hipMemsetAsync(c.d_cand.p, 0, (size_t)nb * kVecCandCap * 8, s));
+        if (p.q8) {
+            VEC_TRY(hipMemsetAsync(c.d_ccnt.p, 0, (size_t)nb * kVecQ8CntStride * sizeof(int32_t), s));
+            vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+            VEC_TRY(hipGetLastError());
+            VEC_TRY(hipMemcpyAsync(cnt_lines.data(), c.d_ccnt.p, (size_t)nb * kVecQ8CntStride * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+        } else {
+            hipLaunchKernelGGL(k_vec_filter, dim3((unsigned)((c.n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s,
+                               c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p);
+            VEC_TRY(hipGetLastError());
+            VEC_TRY(hipMemcpyAsync(cnt, c.d_ccnt.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        VEC_TRY(hipStreamSynchronize(s));
+        if (p.q8)
+            for (int i = 0; i < nb; ++i) cnt[i] = cnt_lines[(size_t)i * kVecQ8CntStride];
+        const int most = *std::max_element(cnt, cnt + nb);
+        c.st[4] = std::max<int64_t>(c.st[4], most);
+        ++c.st[most <= kVecCandCap ? 0 : 2];
+        if (most <= kVecCandCap) {  // every list fits: one sort each
+            const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
+            hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
+                               ns, c.d_dead.p, c.d_cand.p, (int64_t)kVecCandCap, (int64_t)one, one, keep, c.d_keys0.p,
+                               (int64_t)keep);
+            VEC_TRY(hipGetLastError());
+            in = c.d_keys0.p;
+            in_stride = keep;
+        }
+    } else {
+        ++c.st[1];
+    }
+    if (!in) {
+        int64_t n_in = c.n;
+        unsigned long long *out = c.d_keys0.p, *other = c.d_keys1.p;
+        for (bool first = true;; first = false) {
+            const int64_t nsl = (n_in + slice - 1) / slice;
+            const int64_t out_stride = nsl * keep;
+            hipLaunchKernelGGL(k_vec_select, dim3((unsigned)nsl, (unsigned)nb), dim3(256), (size_t)pow2_ceil(slice) * 8, s,
+                               first ? c.d_scores.p : nullptr, ns, c.d_dead.p, in, in_stride, n_in, slice, keep, out,
+                               out_stride);
+            VEC_TRY(hipGetLastError());
+            ++c.st[3];
+            in = out;
+            in_stride = out_stride;
+            n_in = out_stride;
+            std::swap(out, other);
+            if (nsl == 1) break;
+        }
+    }
+    *in_out = in;
+    *in_stride_out = in_stride;
+    return AID_OK;
+}
+
+// Sorted keys of the batch's queries -> the hit columns of queries q0 + i (q0 + qmap[i] with a map).
+static int vec_hits_batch(VecCatalog &c, const unsigned long long *in, int64_t in_stride, int keep, int limit, int nb,
+                          int q0, const int32_t *qmap, hipStream_t s) {
+    hipLaunchKernelGGL(k_vec_hits, dim3((unsigned)nb), dim3(256), 0, s, in, in_stride, keep, limit, c.d_track.p, c.d_off.p,
+                       qmap, c.d_hentry.p + (size_t)q0 * limit, c.d_htrack.p + (size_t)q0 * limit,
+                       c.d_hscore.p + (size_t)q0 * limit, c.d_hoff.p + (size_t)q0 * limit, c.d_nhits.p + q0);
+    VEC_TRY(hipGetLastError());
+    return AID_OK;
+}
+
+// FPSPEC 9 for one batch: the f32 scan, the selection, the hit columns.
+static int vec_f32_batch(VecCatalog &c, const float *dq, int nb, const VecSelPlan &p, int q0, const int32_t *qmap,
+                         hipStream_t s) {
+    if (int rc = vec_scan_batch(c, dq, nb, s)) return rc;
+    unsigned long long *in = nullptr;
+    int64_t in_stride = 0;
+    if (int rc = vec_select_batch(c, nb, p, s, &in, &in_stride)) return rc;
+    return vec_hits_batch(c, in, in_stride, p.keep, p.limit, nb, q0, qmap, s);
+}
+
+// Normalise queries [q0, q0 + nb) into c.d_q, quantise the tiles (FPSPEC 9.1) into d_q8 / d_qs / d_qe and score
+// them against the int8 catalog: approx into c.d_scores [nb rounded up to 32][ns].
+static int vec_q8_scan_batch(VecCatalog &c, const float *dq, int nb, hipStream_t s) {
+    const int dim = c.dim;
+    const int nqt = (nb + 31) / 32;
+    const int64_t n_tiles = (c.n + 31) / 32, ns = n_tiles * 32;
+    VEC_TRY(c.d_q8.reserve((size_t)kVecQueryBatch * dim));
+    VEC_TRY(c.d_qs.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(c.d_qe.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(hipMemsetAsync(c.d_q.p, 0, (size_t)nqt * 32 * dim * sizeof(float), s));
+    hipLaunchKernelGGL(k_vec_normalize, dim3((unsigned)nb), dim3(64), 0, s, dq, (int64_t)nb, dim, c.d_q.p,
+                       (int64_t)0);
+    vec_q8_quantize(c.d_q.p, 0, (int64_t)nqt * 32, dim, c.d_q8.p, c.d_qs.p, c.d_qe.p, s);  // the zero rows too
+    const int chunk = c.force_chunk ? c.force_chunk : kVecScanChunk;
+    vec_q8_scan(c.d_v8.p, c.d_s8.p, n_tiles, std::max(1, chunk / 32), c.d_q8.p, c.d_qs.p, nqt, dim, c.d_scores.p, ns, s);
+    ++c.q8st[5];
+    VEC_TRY(hipGetLastError());
+    return AID_OK;
+}
+
+// FPSPEC 9.1 for all nq queries: per batch the int8 scan, the R best by approx rescored, tau and the threshold, W,
+// W rescored and sorted; the queries whose W is over the cap go through vec_f32_batch as a tile of their own.
+static int vec_search_q8(VecCatalog &c, const float *dq, int nq, const VecSelPlan &pl, hipStream_t s) {
+    const int limit = pl.limit, dim = c.dim;
+    const int64_t ns = (c.n + 31) / 32 * 32;
+    const int R = vec_q8_candidates(limit, c.q8_over);
+    const int wcap = c.force_cand ? c.force_cand : kVecCandCap;
+    VecSelPlan pr;
+    if (int rc = vec_sel_plan(c, R, pr)) return rc;
+    pr.q8 = true;
+    VEC_TRY(c.d_thr.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(c.d_ccnt.reserve((size_t)kVecQueryBatch * kVecQ8CntStride));
+    VEC_TRY(c.d_cand.reserve((size_t)kVecQueryBatch * kVecCandCap));
+    const int64_t r_live = std::min<int64_t>(R, c.n_live);
+    for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
+        const int nb = std::min(kVecQueryBatch, nq - q0);
+        const float *dqb = dq + (size_t)q0 * dim;
+        if (int rc = vec_q8_scan_batch(c, dqb, nb, s)) return rc;
+        unsigned long long *in = nullptr;
+        int64_t in_stride = 0;
+        if (int rc = vec_select_batch(c, nb, pr, s, &in, &in_stride)) return rc;  // the R best by approx
+        VEC_TRY(vec_q8_rescore(c.d_vecs.p, c.d_q.p, dim, in, in_stride, R, nullptr, 0, nb, s));
+        vec_q8_tau(in, in_stride, R, limit, c.d_qe.p, c.q8_E, dim, c.d_thr.p, c.d_ccnt.p, nb, s);
+        VEC_TRY(hipMemsetAsync(c.d_cand.p, 0, (size_t)nb * kVecCandCap * 8, s));
+        vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+        VEC_TRY(hipGetLastError());
+        int32_t cnt[kVecQueryBatch], fb[kVecQueryBatch];
+        std::vector<int32_t> cnt_lines((size_t)nb * kVecQ8CntStride);
+        VEC_TRY(hipMemcpyAsync(cnt_lines.data(), c.d_ccnt.p, cnt_lines.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VEC_TRY(hipStreamSynchronize(s));
+        for (int i = 0; i < nb; ++i) cnt[i] = cnt_lines[(size_t)i * kVecQ8CntStride];
+        int nfb = 0, most = 0;
+        c.q8st[4] += r_live * nb;
+        for (int i = 0; i < nb; ++i) {  // cnt[i] = |W| of query q0 + i
+            c.q8st[2] += cnt[i];
+            c.q8st[3] = std::max<int64_t>(c.q8st[3], cnt[i]);
+            if (cnt[i] > wcap) {
+                fb[nfb++] = i;
+            } else {
+                most = std::max(most, cnt[i]);
+                c.q8st[4] += cnt[i];
+            }
+        }
+        c.q8st[0] += nb - nfb;
+        c.q8st[1] += nfb;
+        if (nfb < nb) {
+            VEC_TRY(vec_q8_rescore(c.d_vecs.p, c.d_q.p, dim, c.d_cand.p, kVecCandCap, most, c.d_ccnt.p, wcap, nb, s));
+            const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
+            hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
+                               ns, c.d_dead.p, c.d_cand.p, (int64_t)kVecCandCap, (int64_t)one, one, pl.keep, c.d_keys0.p,
+                               (int64_t)pl.keep);
+            VEC_TRY(hipGetLastError());
+            // the columns of a query that fell back hold an unfinished list until the f32 route rewrites them below
+            if (int rc = vec_hits_batch(c, c.d_keys0.p, pl.keep, pl.keep, limit, nb, q0, nullptr, s)) return rc;
+        }
+        if (nfb) {
+            VEC_TRY(c.d_fbq.reserve((size_t)kVecQueryBatch * dim));
+            VEC_TRY(c.d_qmap.reserve((size_t)kVecQueryBatch));
+            for (int j = 0; j < nfb; ++j)
+                VEC_TRY(hipMemcpyAsync(c.d_fbq.p + (size_t)j * dim, dqb + (size_t)fb[j] * dim, (size_t)dim * sizeof(float),
+                                       hipMemcpyDeviceToDevice, s));
+            VEC_TRY(hipMemcpyAsync(c.d_qmap.p, fb, (size_t)nfb * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            VEC_TRY(hipStreamSynchronize(s));
+            if (int rc = vec_f32_batch(c, c.d_fbq.p, nfb, pl, q0, c.d_qmap.p, s)) return rc;
+        }
+    }
+    return AID_OK;
+}
+
 // Hit columns of all nq queries on the device: d_hentry / d_htrack / d_hscore / d_hoff [nq][limit], d_nhits [nq].
 static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int location, int limit, hipStream_t s) {
     const size_t nh = (size_t)nq * limit;
@@ -644,79 +932,12 @@ static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int locat
     if (c.n == 0) return AID_OK;
     const float *dq = nullptr;
     if (int rc = vec_stage_queries(c, queries, nq, location, s, &dq)) return rc;
-    const int64_t ns = (c.n + 31) / 32 * 32;
-    // slice-by-slice route: a slice holds at least 2 * limit keys, so every pass shrinks the candidate set
-    const int slice = std::max(c.force_chunk ? c.force_chunk : kVecSelectSlice, 2 * pow2_ceil(limit));
-    const int keep = std::min(limit, slice);
-    const int64_t nsl0 = (c.n + slice - 1) / slice;
-    VEC_TRY(c.d_keys0.reserve((size_t)kVecQueryBatch * nsl0 * keep));
-    VEC_TRY(c.d_keys1.reserve((size_t)kVecQueryBatch * ((nsl0 * keep + slice - 1) / slice) * keep));
-    // threshold route: needs at least `limit` slices, and few enough of them for one sort of their maxima
-    const int mslice = c.force_chunk ? c.force_chunk
-                                     : std::max(kVecMaxSlice, pow2_ceil((int)((c.n + kVecCandCap - 1) / kVecCandCap)));
-    const int64_t msl = (c.n + mslice - 1) / mslice;
-    const bool by_threshold = msl >= limit && msl <= kVecCandCap;
-    if (by_threshold) {
-        VEC_TRY(c.d_smax.reserve((size_t)kVecQueryBatch * msl));
-        VEC_TRY(c.d_thr.reserve((size_t)kVecQueryBatch));
-        VEC_TRY(c.d_ccnt.reserve((size_t)kVecQueryBatch));
-        VEC_TRY(c.d_cand.reserve((size_t)kVecQueryBatch * kVecCandCap));
-    }
+    VecSelPlan pl;
+    if (int rc = vec_sel_plan(c, limit, pl)) return rc;
+    if (c.q8_mode) return vec_search_q8(c, dq, nq, pl, s);
     for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
         const int nb = std::min(kVecQueryBatch, nq - q0);
-        if (int rc = vec_scan_batch(c, dq + (size_t)q0 * c.dim, nb, s)) return rc;
-        unsigned long long *in = nullptr;
-        int64_t in_stride = 0;
-        if (by_threshold) {
-            int32_t cnt[kVecQueryBatch];
-            hipLaunchKernelGGL(k_vec_slice_max, dim3((unsigned)msl, (unsigned)nb), dim3(256), 0, s, c.d_scores.p, ns,
-                               c.d_dead.p, c.n, mslice, (int)msl, c.d_smax.p);
-            const int msp = std::max(2, pow2_ceil((int)msl));
-            hipLaunchKernelGGL(k_vec_threshold, dim3((unsigned)nb), dim3(256), (size_t)msp * 4, s, c.d_smax.p, (int)msl, msp,
-                               limit, c.d_thr.p, c.d_ccnt.p);
-            VEC_TRY(hipMemsetAsync(c.d_cand.p, 0, (size_t)nb * kVecCandCap * 8, s));
-            hipLaunchKernelGGL(k_vec_filter, dim3((unsigned)((c.n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s,
-                               c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p);
-            VEC_TRY(hipGetLastError());
-            VEC_TRY(hipMemcpyAsync(cnt, c.d_ccnt.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            VEC_TRY(hipStreamSynchronize(s));
-            const int most = *std::max_element(cnt, cnt + nb);
-            c.st[4] = std::max<int64_t>(c.st[4], most);
-            ++c.st[most <= kVecCandCap ? 0 : 2];
-            if (most <= kVecCandCap) {  // every list fits: one sort each
-                const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
-                hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
-                                   ns, c.d_dead.p, c.d_cand.p, (int64_t)kVecCandCap, (int64_t)one, one, keep, c.d_keys0.p,
-                                   (int64_t)keep);
-                VEC_TRY(hipGetLastError());
-                in = c.d_keys0.p;
-                in_stride = keep;
-            }
-        } else {
-            ++c.st[1];
-        }
-        if (!in) {
-            int64_t n_in = c.n;
-            unsigned long long *out = c.d_keys0.p, *other = c.d_keys1.p;
-            for (bool first = true;; first = false) {
-                const int64_t nsl = (n_in + slice - 1) / slice;
-                const int64_t out_stride = nsl * keep;
-                hipLaunchKernelGGL(k_vec_select, dim3((unsigned)nsl, (unsigned)nb), dim3(256), (size_t)pow2_ceil(slice) * 8, s,
-                                   first ? c.d_scores.p : nullptr, ns, c.d_dead.p, in, in_stride, n_in, slice, keep, out,
-                                   out_stride);
-                VEC_TRY(hipGetLastError());
-                ++c.st[3];
-                in = out;
-                in_stride = out_stride;
-                n_in = out_stride;
-                std::swap(out, other);
-                if (nsl == 1) break;
-            }
-        }
-        hipLaunchKernelGGL(k_vec_hits, dim3((unsigned)nb), dim3(256), 0, s, in, in_stride, keep, limit, c.d_track.p,
-                           c.d_off.p, c.d_hentry.p + (size_t)q0 * limit, c.d_htrack.p + (size_t)q0 * limit,
-                           c.d_hscore.p + (size_t)q0 * limit, c.d_hoff.p + (size_t)q0 * limit, c.d_nhits.p + q0);
-        VEC_TRY(hipGetLastError());
+        if (int rc = vec_f32_batch(c, dq + (size_t)q0 * c.dim, nb, pl, q0, nullptr, s)) return rc;
     }
     return AID_OK;
 }
@@ -764,6 +985,43 @@ int vec_scores(VecCatalog &c, const float *queries, int nq, int location, float 
         VEC_TRY(hipMemcpy2DAsync(out + (size_t)q0 * c.n, c.n * sizeof(float), c.d_scores.p, ns * sizeof(float),
                                  c.n * sizeof(float), nb, hipMemcpyDeviceToHost, s));
         VEC_TRY(hipStreamSynchronize(s));
+    }
+    return AID_OK;
+}
+
+int vec_scores_i8(VecCatalog &c, const float *queries, int nq, int location, float *approx_out, double *eps_out,
+                  int64_t cap, hipStream_t s) {
+    if (int rc = vec_query_args(c, "aid_vec_scores_i8", queries, nq, location)) return rc;
+    if (!c.q8_mode) return vfail(c, AID_ERR_STATE, "aid_vec_scores_i8: the prefilter is off (aid_vec_prefilter)");
+    if (cap < (int64_t)nq * c.n || (nq > 0 && c.n > 0 && !approx_out) || (nq > 0 && !eps_out))
+        return vfail(c, AID_ERR_INVALID, "aid_vec_scores_i8: approx_out holds fewer than nq * n_entries floats, or null eps_out");
+    if (nq == 0) return AID_OK;
+    const float *dq = nullptr;
+    if (int rc = vec_stage_queries(c, queries, nq, location, s, &dq)) return rc;
+    if (c.n == 0) {  // no int8 planes yet: normalise and quantise the queries alone
+        VEC_TRY(c.d_q8.reserve((size_t)kVecQueryBatch * c.dim));
+        VEC_TRY(c.d_qs.reserve((size_t)kVecQueryBatch));
+        VEC_TRY(c.d_qe.reserve((size_t)kVecQueryBatch));
+    }
+    const int64_t ns = (c.n + 31) / 32 * 32;
+    for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
+        const int nb = std::min(kVecQueryBatch, nq - q0);
+        float qe[kVecQueryBatch];
+        if (c.n) {
+            if (int rc = vec_q8_scan_batch(c, dq + (size_t)q0 * c.dim, nb, s)) return rc;
+            VEC_TRY(hipMemcpy2DAsync(approx_out + (size_t)q0 * c.n, c.n * sizeof(float), c.d_scores.p, ns * sizeof(float),
+                                     c.n * sizeof(float), nb, hipMemcpyDeviceToHost, s));
+        } else {
+            const int nqt = (nb + 31) / 32;
+            VEC_TRY(hipMemsetAsync(c.d_q.p, 0, (size_t)nqt * 32 * c.dim * sizeof(float), s));
+            hipLaunchKernelGGL(k_vec_normalize, dim3((unsigned)nb), dim3(64), 0, s, dq + (size_t)q0 * c.dim, (int64_t)nb,
+                               c.dim, c.d_q.p, (int64_t)0);
+            vec_q8_quantize(c.d_q.p, 0, (int64_t)nqt * 32, c.dim, c.d_q8.p, c.d_qs.p, c.d_qe.p, s);
+            VEC_TRY(hipGetLastError());
+        }
+        VEC_TRY(hipMemcpyAsync(qe, c.d_qe.p, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, s));
+        VEC_TRY(hipStreamSynchronize(s));
+        for (int i = 0; i < nb; ++i) eps_out[q0 + i] = vec_q8_eps(qe[i], c.q8_E, c.dim);
     }
     return AID_OK;
 }
@@ -937,6 +1195,7 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
     c.h_chunk.swap(ch);
     c.h_off.swap(of);
     c.h_dead.swap(dead);
+    if (c.q8_mode) return vec_q8_rebuild(c, s);  // the file holds no int8 form: it follows from the f32 rows
     return AID_OK;
 }
 

@@ -12,6 +12,11 @@ Reported per batch size: median ms per call over the alternations with the sprea
 catalog bytes over the call time as a fraction of the 8 TB/s HBM peak; the MFMA scan against the VALU scan
 (AID_FORCE_VEC_PATH) at 32 queries; and how many of torch's top-50 entries the exact list shares.
 One JSON line per batch size, then one summary line.
+
+--prefilter int8 switches the int8 prefilter on (aid_vec_prefilter, spec/FPSPEC.md 9.1) before the catalog is loaded:
+the same hit lists from an int8 scan with exact rescoring. Each line then carries the prefilter's counters per call
+(queries answered and fallen back, mean and largest |W|); the MFMA / VALU comparison is left to the `off` runs. For
+an A/B, alternate whole runs of `--prefilter off` and `--prefilter int8` on one card (profiles/vec_q8_ab.txt).
 """
 
 from __future__ import annotations
@@ -41,6 +46,8 @@ def main() -> int:
     ap.add_argument("--alternations", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200, help="calls per timed run")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--prefilter", choices=["off", "int8"], default="off")
+    ap.add_argument("--oversample", type=int, default=4)
     args = ap.parse_args()
 
     import torch
@@ -54,6 +61,7 @@ def main() -> int:
     n, dim = args.entries, args.dim
     eng = Engine(16000, device=0)
     L.check(eng._lib.aid_vec_reset(eng._h, dim))
+    L.check(eng._lib.aid_vec_prefilter(eng._h, 1 if args.prefilter == "int8" else 0, args.oversample))
     cat = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
     step = 50_000
     for a in range(0, n, step):
@@ -97,15 +105,18 @@ def main() -> int:
         run_engine(q, args.warmup)
         run_torch(qn, args.warmup)
         te, tt = [], []
+        pst = (ctypes.c_int64 * 6)()
+        L.check(eng._lib.aid_vec_prefilter_stats(eng._h, pst, 6, 1))
         for _ in range(args.alternations):
             ms, hits = run_engine(q, args.steps)
             te.append(ms)
             ms, ti = run_torch(qn, args.steps)
             tt.append(ms)
+        L.check(eng._lib.aid_vec_prefilter_stats(eng._h, pst, 6, 1))
         shared = float(np.mean([len(set(hits[k]["entry"].tolist()) & set(ti[k].tolist())) / args.limit for k in range(nq)]))
         e, t = stats(te), stats(tt)
         line = {"queries": nq, "entries": n, "dim": dim, "limit": args.limit, "alternations": args.alternations,
-                "steps": args.steps, "engine": e, "torch_topk": t,
+                "steps": args.steps, "prefilter": args.prefilter, "engine": e, "torch_topk": t,
                 "engine_queries_per_s": round(nq / (e["median_ms"] * 1e-3), 1),
                 "torch_queries_per_s": round(nq / (t["median_ms"] * 1e-3), 1),
                 "engine_hbm_fraction": round(cat_bytes / (e["median_ms"] * 1e-3) / HBM_PEAK, 4),
@@ -113,7 +124,13 @@ def main() -> int:
                 "engine_over_torch": round(e["median_ms"] / t["median_ms"], 3),
                 "torch_spread_rel": round((t["max_ms"] - t["min_ms"]) / t["median_ms"], 3),
                 "top_entries_shared_with_torch": round(shared, 4), "nearest_found": bool(hits[0]["entry"][0] == 12345)}
-        if nq == 32:  # the two scans against each other
+        if args.prefilter == "int8":
+            calls = args.alternations * args.steps
+            line["prefilter_per_call"] = {"answered": pst[0] / calls, "fell_back": pst[1] / calls,
+                                          "w_mean": round(pst[2] / max(1, pst[0] + pst[1]), 1), "w_max": int(pst[3]),
+                                          "rescored_pairs": pst[4] / calls, "i8_scans": pst[5] / calls,
+                                          "oversample": args.oversample}
+        elif nq == 32:  # the two scans against each other
             ab = {}
             for name, path in (("mfma", 1), ("valu", 2)):
                 eng.force("vec_path", path)
@@ -127,7 +144,7 @@ def main() -> int:
         "metric": f"exact top-{args.limit} search over {n} x {dim} float32 vectors, ms per call (median), 1 GPU",
         "value": summary.get("32", next(iter(summary.values())))["engine_ms"], "unit": "ms per 32-query call",
         "higher_is_better": False, "n_gpus": 1, "dtype": "float32 (pinned fmaf chain)", "data": "synthetic (random normal vectors)",
-        "by_queries": summary,
+        "prefilter": args.prefilter, "by_queries": summary,
     }), flush=True)
     eng.close()
     return 0

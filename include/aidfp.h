@@ -126,6 +126,8 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
 #define AID_FORCE_ROWS_MERGE 13    /* live index: 0 default (the host-row query calls merge a query's two row lists on the
                                       host), 1: they merge on the device (k_rows_merge, as aid_exact_lane always
                                       does) and copy the merged rows out (tests: constructed lists through the kernel) */
+#define AID_FORCE_VEC_CAND 14      /* int8 prefilter: 0 default (4096), else the cap on |W| in [1, 4096] above which a
+                                      query falls back to the f32 scan (tests: fallbacks on a small catalog) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
@@ -428,6 +430,23 @@ int aid_vec_load(aid_engine *e, const char *path);
    sum; it may exceed 4096, which is what [2] counts), [5] catalog reallocations that copied stored rows, [6] MFMA
    scan launches and [7] VALU scan launches (aid_vec_scores counts in these two as well). */
 int aid_vec_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
+/* int8 prefilter (spec/FPSPEC.md 9.1; K9q, csrc/vector_q8.hip), off by default. mode 1 keeps an int8 copy of the
+   catalog (dim + 8 bytes per entry beside the f32 rows, which stay: rescoring reads them), and aid_vec_search /
+   aid_vibe_lane then scan that copy, rescore the entries that a proven error bound cannot rule out with FPSPEC 9's
+   chain, and fall back to the f32 scan for a query with more than 4096 such entries. Hit lists, score bits and rows
+   are the same with it on and off; only the work differs. oversample in [1, 64]: the first-stage candidates are
+   R = min(1024, oversample * limit). Entries already stored are quantised by the call; mode 0 frees the copy. The
+   save file does not change: the int8 form follows from the stored rows and is rebuilt by aid_vec_load. */
+int aid_vec_prefilter(aid_engine *e, int32_t mode, int32_t oversample);
+/* Debug and parity view of the prefilter, as aid_vec_scores is of the scan: approx [nq][n_entries] to host
+   `approx_out` (capacity `cap` floats) and eps [nq] to host `eps_out`. AID_ERR_STATE while the prefilter is off. */
+int aid_vec_scores_i8(aid_engine *e, const float *queries, int32_t nq, int32_t location, float *approx_out,
+                      double *eps_out, int64_t cap);
+/* Cumulative prefilter counters since the last reset (the first n of 6): out[0] queries answered by the prefilter,
+   [1] queries that fell back to the f32 scan, [2] the sum and [3] the largest of |W| over both kinds, [4] pairs
+   rescored with the FPSPEC 9 chain (first-stage candidates and the W of the answered queries), [5] int8 scan
+   launches (aid_vec_scores_i8 counts here as well). The selection over approx also counts in aid_vec_stats. */
+int aid_vec_prefilter_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
 
 /* ---- CLAP log-mel front end (spec/FPSPEC.md 10; K10, csrc/mel.hip) ----
  * What the reference computes on the host before its CLAP model sees a sample: chunk_audio (10 s chunks, 5 s hop,
