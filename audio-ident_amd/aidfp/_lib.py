@@ -32,6 +32,7 @@ AID_K_COUNT = 16
 AID_MEL_FRAMES, AID_MEL_BANDS, AID_MEL_BINS, AID_MEL_WINDOW = 1001, 64, 513, 480000
 AID_MEL_ZERO, AID_MEL_REPEATPAD = 0, 1
 AID_MEL_BANK_SLANEY, AID_MEL_BANK_HTK, AID_MEL_BANK_CUSTOM = 0, 1, 2
+AID_CHROMA_RATE, AID_CHROMA_BANDS, AID_CHROMA_RUN = 11025, 12, 4
 KERNEL_NAMES = ["stft_power", "peak_pick", "landmark_count", "landmark_write", "synth", "match", "resample",
                 "dedup", "index_build", "vote_hist", "hot_scan", "vote_final", "resample_speeds", "speed_select", "rows_merge", "index_merge"]
 
@@ -210,6 +211,13 @@ SIGNATURES = [
     ("aid_mel_filters", ctypes.c_int, [P, P]),
     ("aid_mel_plan", ctypes.c_int, [P, I32, I32, I64, P, P, I64]),
     ("aid_logmel", ctypes.c_int, [P, P, P, P, I32, I32, I32, I64, P, I64, I32, P, P, P]),
+    ("aid_chroma_len", I64, [I64]),
+    ("aid_chroma_plan", ctypes.c_int, [P, I32, P, P, P]),
+    ("aid_chroma", ctypes.c_int, [P, P, P, I32, I32, P, P, I64, I32, P, P]),
+    ("aid_chroma_rows", ctypes.c_int, [P, P, P, I32, I32, P, P, I64, P, P]),
+    ("aid_chroma_words", ctypes.c_int, [P, P, P, I32, I32, P, P, I64, P]),
+    ("aid_dedup_add_at", ctypes.c_int, [P, P, P, P, I32, I32]),
+    ("aid_dedup_scan_at", ctypes.c_int, [P, P, P, P, I32, I32, P, P]),
     ("aid_profile_enable", ctypes.c_int, [P, I32]),
     ("aid_profile_read", ctypes.c_int, [P, P, P, I32]),
     ("aid_profile_select", ctypes.c_int, [P, ctypes.c_uint32]),
@@ -223,8 +231,9 @@ SIGNATURES += [(name + "_s16", res, args) for name, res, args in SIGNATURES
 # aid_exact_lane_s16): aid_resample_s16_speeds, aid_exact_lane_s16_speeds
 SIGNATURES += [(name[:-len("_speeds")] + "_s16_speeds", res, args) for name, res, args in SIGNATURES
                if name in ("aid_resample_speeds", "aid_exact_lane_speeds")]
-# K10's int16 form: aid_logmel_pcm16
-SIGNATURES += [(name + "_pcm16", res, args) for name, res, args in SIGNATURES if name == "aid_logmel"]
+# K10's and K11's int16 forms: aid_logmel_pcm16, aid_chroma_pcm16, aid_chroma_rows_pcm16
+SIGNATURES += [(name + "_pcm16", res, args) for name, res, args in SIGNATURES
+               if name in ("aid_logmel", "aid_chroma", "aid_chroma_rows")]
 PCM_FORMATS = ("f32", "s16")
 
 _lib = None

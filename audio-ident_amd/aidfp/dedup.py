@@ -11,7 +11,9 @@ winner (earliest of the best, strict >) as the reference (tests/test_gpu_dedup.p
 vectors captured from the reference, tests/golden/ref_dedup.json).
 
 Kept from the reference unchanged in meaning: `f32le_to_s16le` (:41-53; numpy, host),
-`check_file_duplicate` stays a SQL lookup (not on the GPU), and fpcalc itself stays external.
+`check_file_duplicate` stays a SQL lookup (not on the GPU). fpcalc itself stays external; aidfp/chroma.py is the
+engine's own fingerprint in the same raw form (FPSPEC 11; parity with fpcalc unpinned), which `add_pcm` / `check_pcm`
+feed to this catalog without the words leaving the device.
 """
 
 from __future__ import annotations
@@ -23,7 +25,7 @@ from typing import Sequence
 
 import numpy as np
 
-from ._lib import check
+from ._lib import AID_PCM_DEVICE, check
 
 
 def f32le_to_s16le(pcm_f32le: bytes) -> bytes:
@@ -104,6 +106,44 @@ class ContentIndex:
         if ids[0] is not None and sims[0] >= threshold:
             return ids[0]
         return None
+
+    # ---- PCM in, fingerprinted by K11 (aidfp/chroma.py; FPSPEC 11): the words go from K11 to K7 on the device ----
+    def _printer(self):
+        from .chroma import ChromaPrinter
+
+        return ChromaPrinter(self.eng)
+
+    def add_pcm(self, ids: Sequence, clips: Sequence, sr: int, durations: Sequence[float | None], fmt: str = "f32",
+                channels: int = 1) -> int:
+        """`add` for tracks given as PCM: each is fingerprinted on the device and stored; tracks without a duration
+        or too short for a word are skipped, as `add` skips those without a fingerprint. Returns how many were stored."""
+        rows = [(i, c, float(d)) for i, c, d in zip(ids, clips, durations) if d is not None]
+        if not rows:
+            return 0
+        words, woff = self._printer().fingerprints_device([c for _, c, _ in rows], sr, fmt, channels)
+        keep = [k for k in range(len(rows)) if woff[k + 1] > woff[k]]  # the others hold no word: offsets stay packed
+        if not keep:
+            return 0
+        off = np.ascontiguousarray([woff[k] for k in keep] + [woff[-1]], dtype=np.int64)
+        dur = np.ascontiguousarray([rows[k][2] for k in keep], dtype=np.float64)
+        check(self.eng._lib.aid_dedup_add_at(self.eng._h, ctypes.c_void_p(words.data_ptr()), _p(off), _p(dur),
+                                             len(keep), AID_PCM_DEVICE))
+        self.ids += [rows[k][0] for k in keep]
+        return len(keep)
+
+    def check_pcm(self, clip, sr: int, duration: float, threshold: float = 0.85, fmt: str = "f32", channels: int = 1,
+                  with_score: bool = False):
+        """`check` for an upload given as PCM; None when it is too short for a word (the reference then has no
+        fingerprint to check). with_score: (id or None, best score) instead."""
+        words, woff = self._printer().fingerprints_device([clip], sr, fmt, channels)
+        if woff[1] == 0:
+            return (None, 0.0) if with_score else None
+        dur = np.ascontiguousarray([float(duration)], dtype=np.float64)
+        idx, sim = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.float64)
+        check(self.eng._lib.aid_dedup_scan_at(self.eng._h, ctypes.c_void_p(words.data_ptr()), _p(woff), _p(dur), 1,
+                                              AID_PCM_DEVICE, _p(idx), _p(sim)))
+        hit = self.ids[idx[0]] if idx[0] >= 0 and sim[0] >= threshold else None
+        return (hit, float(sim[0])) if with_score else hit
 
     def check_batch(self, fingerprints: Sequence[str], durations: Sequence[float], threshold: float = 0.85):
         ids, sims = self.scan(fingerprints, durations)

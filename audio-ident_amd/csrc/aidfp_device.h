@@ -99,6 +99,22 @@ __device__ __forceinline__ void dft16(float2 (&v)[16], const float2 (&t16)[10]) 
     for (int i = 0; i < 16; ++i) v[i] = o[i];
 }
 
+// FPSPEC 10 DFT8: two DFT4 over the even and odd inputs, W8 twiddles on the odd half, one radix-2 pass
+__device__ __forceinline__ void dft8(float2 (&v)[8], float2 w1, float2 w3) {
+    dft4(v[0], v[2], v[4], v[6]);
+    dft4(v[1], v[3], v[5], v[7]);
+    const float2 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
+    const float2 o0 = v[1], o1 = cmul(v[3], w1), o2 = make_float2(v[5].y, -v[5].x), o3 = cmul(v[7], w3);
+    v[0] = cadd(e0, o0);
+    v[1] = cadd(e1, o1);
+    v[2] = cadd(e2, o2);
+    v[3] = cadd(e3, o3);
+    v[4] = csub(e0, o0);
+    v[5] = csub(e1, o1);
+    v[6] = csub(e2, o2);
+    v[7] = csub(e3, o3);
+}
+
 // Orders a wave's own LDS exchange (write -> read by other lanes of the SAME wave). A wave's
 // LDS instructions are executed in issue order (LLVM AMDGPU memory model: LDS accesses of one
 // wavefront stay in order), so only the compiler must be kept from moving accesses across

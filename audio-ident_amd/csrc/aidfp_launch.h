@@ -81,6 +81,13 @@ struct MelChunkDev;  // aidfp_mel.h
 struct MelTables;
 void launch_logmel(const void *pcm, bool s16, const MelChunkDev *chunks, int64_t chunk0, int64_t n, const MelTables *tab,
                    const float *wc, float *out, hipStream_t s);
+struct ChromaRowBlock;  // aidfp_chroma_plan.h
+struct ChromaItemBlock;
+struct ChromaTables;  // aidfp_chroma.h
+void launch_chroma_rows(const void *pcm, bool s16, const ChromaRowBlock *blocks, int64_t block0, int64_t n,
+                        const ChromaTables *tab, float *rows, hipStream_t s);
+void launch_chroma_words(const float *rows, const ChromaItemBlock *blocks, int64_t block0, int64_t n,
+                         const ChromaTables *tab, bool raw, uint32_t *words, hipStream_t s);
 void launch_rows_scatter(const int32_t *src, const int32_t *order, int n, int mr, int32_t *dst, hipStream_t s);
 // the two row lists of each of nq queries over the live index merged into the first (index.hip k_rows_merge)
 void launch_rows_merge(int32_t *a, int32_t *na, const int32_t *b, const int32_t *nb, int nq, int mr, hipStream_t s);

@@ -448,8 +448,11 @@ static int check_offsets(const int64_t *off, int32_t n, const char *what) {
     return AID_OK;
 }
 
-int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t n) {
-    if (!e || n < 0 || (n > 0 && (!offsets || !durations))) return fail(AID_ERR_INVALID, "aid_dedup_add: bad argument");
+// words: host or device (loc); a device array is copied in stream order on the engine's own stream
+static int dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t n,
+                     int32_t loc) {
+    if (!e || n < 0 || (n > 0 && (!offsets || !durations)) || (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE))
+        return fail(AID_ERR_INVALID, "aid_dedup_add: bad argument");
     if (n == 0) return AID_OK;
     if (int rc = check_offsets(offsets, n, "aid_dedup_add")) return rc;
     const int64_t nw = offsets[n];
@@ -462,7 +465,9 @@ int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, 
     HIP_TRY(e->dd_dur.grow_keep((size_t)e->dd_n, (size_t)(e->dd_n + n), s));
     std::vector<int64_t> off(n + 1);
     for (int32_t i = 0; i <= n; ++i) off[i] = e->dd_nw + offsets[i];
-    if (nw > 0) HIP_TRY(hipMemcpyAsync(e->dd_words.p + e->dd_nw, words, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (nw > 0)
+        HIP_TRY(hipMemcpyAsync(e->dd_words.p + e->dd_nw, words, nw * sizeof(uint32_t),
+                               loc == AID_PCM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->dd_off.p + e->dd_n, off.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->dd_dur.p + e->dd_n, durations, n * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -471,9 +476,20 @@ int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, 
     return AID_OK;
 }
 
-int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t nq,
-                   int64_t *best_idx, double *best_sim) {
-    if (!e || nq < 0 || (nq > 0 && (!offsets || !durations || !best_idx || !best_sim)))
+int aid_dedup_add(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t n) {
+    return dedup_add(e, words, offsets, durations, n, AID_PCM_HOST);
+}
+
+int aid_dedup_add_at(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t n,
+                     int32_t location) {
+    return dedup_add(e, words, offsets, durations, n, location);
+}
+
+// words: host (copied to the scan's scratch) or device (K7 reads them in place)
+static int dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t nq,
+                      int32_t loc, int64_t *best_idx, double *best_sim) {
+    if (!e || nq < 0 || (nq > 0 && (!offsets || !durations || !best_idx || !best_sim)) ||
+        (loc != AID_PCM_HOST && loc != AID_PCM_DEVICE))
         return fail(AID_ERR_INVALID, "aid_dedup_scan: bad argument");
     if (nq == 0) return AID_OK;
     if (int rc = check_offsets(offsets, nq, "aid_dedup_scan")) return rc;
@@ -496,13 +512,17 @@ int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets,
     HIP_TRY(e->dq_idx.reserve((size_t)nq));
     HIP_TRY(e->dq_psim.reserve((size_t)nq * nc));
     HIP_TRY(e->dq_pidx.reserve((size_t)nq * nc));
-    if (nw > 0) HIP_TRY(hipMemcpyAsync(e->dq_words.p, words, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const uint32_t *qw = e->dq_words.p;
+    if (loc == AID_PCM_DEVICE && nw > 0)
+        qw = words;
+    else if (nw > 0)
+        HIP_TRY(hipMemcpyAsync(e->dq_words.p, words, nw * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->dq_off.p, offsets, (nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->dq_lo.p, lo.data(), nq * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->dq_hi.p, hi.data(), nq * sizeof(double), hipMemcpyHostToDevice, s));
     {
         ProfScope ps(e, AID_K_DEDUP, s);
-        launch_dedup_scan(e->dd_words.p, e->dd_off.p, e->dd_dur.p, e->dd_n, e->dq_words.p, e->dq_off.p, e->dq_lo.p,
+        launch_dedup_scan(e->dd_words.p, e->dd_off.p, e->dd_dur.p, e->dd_n, qw, e->dq_off.p, e->dq_lo.p,
                           e->dq_hi.p, nq, e->dq_psim.p, e->dq_pidx.p, e->dq_sim.p, e->dq_idx.p, s);
     }
     HIP_TRY(hipGetLastError());
@@ -510,6 +530,16 @@ int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets,
     HIP_TRY(hipMemcpyAsync(best_sim, e->dq_sim.p, nq * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return AID_OK;
+}
+
+int aid_dedup_scan(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t nq,
+                   int64_t *best_idx, double *best_sim) {
+    return dedup_scan(e, words, offsets, durations, nq, AID_PCM_HOST, best_idx, best_sim);
+}
+
+int aid_dedup_scan_at(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations,
+                      int32_t nq, int32_t location, int64_t *best_idx, double *best_sim) {
+    return dedup_scan(e, words, offsets, durations, nq, location, best_idx, best_sim);
 }
 
 int aid_dedup_pairs(aid_engine *e, const uint32_t *a, const int64_t *a_off, const uint32_t *b, const int64_t *b_off,

@@ -4,7 +4,8 @@
 // profiling. extract.cpp: extraction and its results (aidfp_extract.h). index_host.cpp: the hash index
 // (aidfp_index.h). index_exchange.cpp: aid_comm and the index exchange (the only file that includes RCCL).
 // query.cpp: K5, the query entry points, the exact lane. speed.cpp: the speed fan-out and the speed lane
-// (aidfp_speed_plan.h). mel.cpp: the CLAP log-mel front end (aidfp_mel_plan.h, aidfp_mel.h). Nothing here is part of the C ABI.
+// (aidfp_speed_plan.h). mel.cpp: the CLAP log-mel front end (aidfp_mel_plan.h, aidfp_mel.h). chroma.cpp: the content fingerprint
+// (aidfp_chroma_plan.h, aidfp_chroma.h). Nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,7 @@
 
 #include "../../include/aidfp.h"
 #include "aidfp_buffers.h"
+#include "aidfp_chroma.h"
 #include "aidfp_device.h"
 #include "aidfp_extract.h"
 #include "aidfp_index.h"
@@ -146,6 +148,7 @@ struct aid_engine {
     DevBuf<uint32_t> dq_words, dq_words2;
     DevBuf<int64_t> dq_off, dq_off2, dq_idx, dq_pidx;
     DevBuf<double> dq_lo, dq_hi, dq_sim, dq_psim;
+    ChromaState chroma;  // content fingerprint (FPSPEC 11): tables, block lists, staging, rows (chroma.cpp)
     MelState mel;    // CLAP log-mel front end (FPSPEC 10): tables, filter bank, chunk table, staging (mel.cpp)
     VecCatalog vec;  // vector lane (FPSPEC 9): chunk-embedding catalog + its scratch (csrc/vector.hip)
     size_t hist_zero_cap = 0;  // q_hist capacity known to be all-zero

@@ -38,22 +38,6 @@ static_assert(kMelHop % 2 == 0, "a frame's first sample pair must be 8-byte alig
 __device__ __forceinline__ float mel_load(const float *p) { return *p; }
 __device__ __forceinline__ float mel_load(const int16_t *p) { return (float)*p * 0x1p-15f; }  // FPSPEC 8.1
 
-// FPSPEC 10 DFT8: two DFT4 over the even and odd inputs, W8 twiddles on the odd half, one radix-2 pass
-__device__ __forceinline__ void dft8(float2 (&v)[8], float2 w1, float2 w3) {
-    dft4(v[0], v[2], v[4], v[6]);
-    dft4(v[1], v[3], v[5], v[7]);
-    const float2 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-    const float2 o0 = v[1], o1 = cmul(v[3], w1), o2 = make_float2(v[5].y, -v[5].x), o3 = cmul(v[7], w3);
-    v[0] = cadd(e0, o0);
-    v[1] = cadd(e1, o1);
-    v[2] = cadd(e2, o2);
-    v[3] = cadd(e3, o3);
-    v[4] = csub(e0, o0);
-    v[5] = csub(e1, o1);
-    v[6] = csub(e2, o2);
-    v[7] = csub(e3, o3);
-}
-
 // FPSPEC 10 "dB": 10 log10(M) of a normal positive M
 __device__ __forceinline__ float mel_db10(float M) {
     const uint32_t b = __float_as_uint(M);

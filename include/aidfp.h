@@ -501,6 +501,53 @@ int aid_logmel_pcm16(aid_engine *e, const int16_t *pcm, const int64_t *clip_off,
                         int64_t out_cap_chunks, int32_t out_location, aid_mel_chunk *meta, int64_t *n_chunks,
                         void *stream);
 
+/* ---- content fingerprint (spec/FPSPEC.md 11) ----
+ * Replaces the `fpcalc -raw` subprocess of app/audio/dedup.py:53-124 (`generate_chromaprint`) by K11: mono PCM at
+ * 11025 Hz (resample first: aid_resample) -> 32-bit words in the raw-Chromaprint form aid_dedup_* takes. The spec is
+ * the engine's own; PARITY WITH fpcalc IS UNPINNED (no fpcalc was at hand to compare with), so do not mix these
+ * words with a database filled by fpcalc. Clip c = pcm[clip_off[c] .. clip_off[c+1]) (HOST offsets, n_clips + 1,
+ * non-decreasing); a clip of n samples has 1 + (n - 4096) / 1365 frames and max(0, frames - 19) words, the first
+ * at n = 30031. No sample outside a clip is read. */
+#define AID_CHROMA_RATE 11025
+#define AID_CHROMA_BANDS 12
+#ifndef AID_CHROMA_RUN /* frames of one K11a workgroup (tests aim at its edges); diagnostic builds set others */
+#define AID_CHROMA_RUN 4
+#endif
+/* words of a clip of n samples. No device. */
+int64_t aid_chroma_len(int64_t n);
+/* word offsets (word_off_out: int64[n_clips + 1] or NULL), frames and words of a batch of clip lengths. No device. */
+int aid_chroma_plan(const int64_t *lengths, int32_t n_clips, int64_t *word_off_out, int64_t *n_frames,
+                    int64_t *n_words);
+/* The words of every clip, packed in clip order. pcm: host or device (`location`, AID_PCM_*; host PCM is staged by
+   one copy). words_out: host or device (`out_location`), capacity cap_words; word_off_out: HOST int64[n_clips + 1]
+   or NULL. *n_words is always set; more words than cap_words: AID_ERR_INVALID and nothing else written. Device
+   output is asynchronous on `stream` (NULL: the engine's own stream, which aid_dedup_*_at run on too). */
+int aid_chroma(aid_engine *e, const float *pcm, const int64_t *clip_off, int32_t n_clips, int32_t location,
+               uint32_t *words_out, int64_t *word_off_out, int64_t cap_words, int32_t out_location, int64_t *n_words,
+               void *stream);
+/* The same over int16 PCM (FPSPEC 8.1: x = q / 32768), offsets in int16 samples. */
+int aid_chroma_pcm16(aid_engine *e, const int16_t *pcm, const int64_t *clip_off, int32_t n_clips, int32_t location,
+                   uint32_t *words_out, int64_t *word_off_out, int64_t cap_words, int32_t out_location,
+                   int64_t *n_words, void *stream);
+/* K11a alone, for tests and diagnosis: the chroma rows C[frames][12] of every clip (rows_out: HOST floats, capacity
+   cap_rows rows; row_off_out: HOST int64[n_clips + 1] or NULL). Synchronous. */
+int aid_chroma_rows(aid_engine *e, const float *pcm, const int64_t *clip_off, int32_t n_clips, int32_t location,
+                    float *rows_out, int64_t *row_off_out, int64_t cap_rows, int64_t *n_rows, void *stream);
+int aid_chroma_rows_pcm16(aid_engine *e, const int16_t *pcm, const int64_t *clip_off, int32_t n_clips, int32_t location,
+                        float *rows_out, int64_t *row_off_out, int64_t cap_rows, int64_t *n_rows, void *stream);
+/* K11b alone on the caller's HOST rows: clip c = rows [row_off[c], row_off[c+1]) of 12 floats. raw_features = 0:
+   the rows are C (a word reads 20 of them); != 0: they are F, smoothing and normalisation skipped (a word reads 16).
+   A word never reads another clip's rows. All arrays host; synchronous. */
+int aid_chroma_words(aid_engine *e, const float *rows, const int64_t *row_off, int32_t n_clips, int32_t raw_features,
+                     uint32_t *words_out, int64_t *word_off_out, int64_t cap_words, int64_t *n_words);
+/* aid_dedup_add / aid_dedup_scan with the word array on the host or the device (`location`; offsets and durations
+   stay host arrays): fingerprints made by aid_chroma on the device reach K7 without a round trip. Device words must
+   be complete on the engine's own stream (aid_chroma with stream NULL) or before the call. */
+int aid_dedup_add_at(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations, int32_t n,
+                     int32_t location);
+int aid_dedup_scan_at(aid_engine *e, const uint32_t *words, const int64_t *offsets, const double *durations,
+                      int32_t nq, int32_t location, int64_t *best_idx, double *best_sim);
+
 /* ---- native multi-GPU exchange (SURVEY.md 8b "aid_allgather_index", 8e) ----
  * One process per GPU. Rank 0 calls aid_comm_id, the host hands the 128 id bytes to every
  * rank (any side channel: torch.distributed store, MPI, a file), then every rank calls
