@@ -9,6 +9,8 @@ namespace aid {
 struct Extractor {
     DevBuf<float> pcm_stage, power;  // host PCM staged as one copy (raw bytes to both formats); one clip group's plane
     DevBuf<uint64_t> mask, hotw;     // the call's peak bits; K1 -> K2: per power row, bit hot_bit(c) = chunk c is > thr
+    // K2 -> K3 (aidfp_layout.h): per K2 strip, 32 rows and quarter one word; a mask quarter without its bit is stale
+    DevBuf<uint32_t> rowflags;
     // FPSPEC 5.1 (peak_rel > 0): per clip the bits of max Q over its plane: zeroed ahead of K1, raised by it, read by K2
     DevBuf<uint32_t> clip_qmax;
     DevBuf<uint32_t> k2_cold;  // K2: strip-cold wave counters (64) and twice-walked strip counters (64), summed and reset by K3

@@ -70,6 +70,7 @@ struct ClipGroup {
     int64_t frame0 = 0, frames = 0;     // its rows of the call's power and mask planes
     int64_t strips = 0, k1_strips = 0;  // K2 strips at strip_len (strip_base restarts per group); K1 wave-strips
     int strip_len = 0;
+    int64_t flag_base = 0;  // its first row-flag word (aidfp_layout.h: strips x flag_words_per_strip(strip_len) words)
 };
 
 struct ExtractPlan {
@@ -77,7 +78,7 @@ struct ExtractPlan {
     std::vector<int64_t> frames, hash_base;  // per clip, as in desc (hash_base is what aid_result_device hands out)
     std::vector<ClipGroup> groups;           // at least one, also for a call without clips
     int n_clips = 0, width = 4;
-    int64_t total_frames = 0, strips = 0, chunks = 0, records = 0;
+    int64_t total_frames = 0, strips = 0, chunks = 0, records = 0, flag_words = 0;
     int64_t staged = 0;       // samples of host PCM to stage: the clips' span as one copy (0 for device PCM)
     bool empty_clip = false;  // a clip without frames gets no count from K3: zero the counts first
     // K3 (landmarks.hip): a clip of several chunks needs the COUNT pass; when every clip is exactly one chunk, a
@@ -109,7 +110,7 @@ inline void plan_extract(ExtractPlan &p, const int64_t *offsets, const int64_t *
         acc += p.frames[c];
     }
     p.groups.push_back({first, n_clips - first});
-    p.total_frames = p.strips = p.chunks = p.records = 0;
+    p.total_frames = p.strips = p.chunks = p.records = p.flag_words = 0;
     p.staged = loc == AID_PCM_HOST && n_clips > 0 ? clip_end(n_clips - 1) - offsets[0] : 0;
     p.empty_clip = p.multi_chunk = false;
     p.one_chunk_each = n_clips > 0;
@@ -117,12 +118,14 @@ inline void plan_extract(ExtractPlan &p, const int64_t *offsets, const int64_t *
     for (ClipGroup &g : p.groups) {
         g.strip_len = peak_strip_len(p.frames.data() + g.first, g.n, std::max<int64_t>(1, (int64_t)(slots * slots_x)));
         g.frame0 = p.total_frames;
+        g.flag_base = p.flag_words;
         for (int c = g.first; c < g.first + g.n; ++c) {
             const int64_t F = p.frames[c], nck = (F + kHashChunk - 1) / kHashChunk;
             // pcm_off: device PCM is read in place (odd offsets: K1's float2 loads need dword alignment only), host PCM
             // from its staged span. strip_base counts within the group (K2 runs per group), other bases over the call
             p.desc[c] = {loc == AID_PCM_DEVICE ? offsets[c] : offsets[c] - offsets[0], F, p.total_frames, g.strips,
-                         p.chunks, p.records, hash_capacity(F), k1_strips};
+                         p.chunks, p.records, hash_capacity(F), k1_strips,
+                         g.flag_base + g.strips * flag_words_per_strip(g.strip_len), g.strip_len};
             p.hash_base[c] = p.records;
             p.empty_clip |= F == 0;
             p.multi_chunk |= nck > 1;
@@ -136,10 +139,11 @@ inline void plan_extract(ExtractPlan &p, const int64_t *offsets, const int64_t *
             p.records += hash_capacity(F);
         }
         p.strips += g.strips;
+        p.flag_words += g.strips * flag_words_per_strip(g.strip_len);
     }
 }
 
-// the descriptor cache's criterion: kernels take all but strip length, group bounds and PCM pointer from these bytes
+// the descriptor cache's criterion: kernels take all but the group bounds and the PCM pointer from these bytes
 inline bool desc_differ(const ClipDesc *a, size_t na, const ClipDesc *b, size_t nb) {
     return na != nb || (na > 0 && memcmp(a, b, na * sizeof(ClipDesc)) != 0);
 }

@@ -13,11 +13,11 @@ void launch_stft_power(const void *pcm, bool s16, const ClipDesc *clips, int n_c
 int peak_pick_blocks_per_cu(int width);
 void launch_peak_pick(int width, const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
                       int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
-                      const uint32_t *clip_qmax, float rel, hipStream_t s);
-void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
-                      int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
-                      uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips, bool one_chunk_each,
-                      hipStream_t s);
+                      const uint32_t *clip_qmax, float rel, uint32_t *rowflags, hipStream_t s);
+void launch_landmarks(const uint64_t *mask, const uint32_t *rowflags, const ClipDesc *clips, int n_clips,
+                      int64_t total_chunks, int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write,
+                      uint32_t *k2_cold, uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips,
+                      bool one_chunk_each, hipStream_t s);
 void launch_synth(float *out, const uint32_t *tracks, const int64_t *starts, int n_clips, int64_t n, int sr,
                   int noise_a, uint32_t salt, int fmax_hz, bool envelope, const int16_t *sin_tab, hipStream_t s);
 // (the launch shape and what is refused: aidfp_resample_plan.h)

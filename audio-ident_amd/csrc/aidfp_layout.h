@@ -89,7 +89,14 @@ inline int64_t num_frames(int64_t n, int hop) { return (hop <= 0 || n < kN) ? 0 
 inline int64_t peak_capacity(int64_t F) { return 64 * ((F + 7) / 8); }
 inline int64_t hash_capacity(int64_t F) { return kFan * peak_capacity(F); }
 
-// Per-clip descriptor uploaded with each extraction call (struct of 8 x int64).
+// K2 -> K3 row flags (u32 words beside the mask plane): the rows of a K2 strip of length L take nw = ceil(L / 32)
+// words per 256-bin quarter; word j, quarter q of a clip's strip s lies at flag_base + (s * nw + j) * 4 + q, so the
+// four quarters of the same 32 rows are one aligned 16-byte unit. Bit b is set iff row 32 j + b of the strip has a
+// peak in quarter q (mask words 4q .. 4q+3 of the row not all zero). A mask word whose bit is clear is NOT written:
+// it holds whatever an earlier call left there, and every reader goes by the flags.
+constexpr int64_t flag_words_per_strip(int strip_len) { return 4 * (((int64_t)strip_len + 31) / 32); }
+
+// Per-clip descriptor uploaded with each extraction call (struct of 10 x int64).
 struct ClipDesc {
     int64_t pcm_off;     // first sample of the clip in the PCM buffer (odd: 4-byte aligned float2 loads)
     int64_t frames;      // F
@@ -99,6 +106,8 @@ struct ClipDesc {
     int64_t hash_base;   // first record slot of the clip in the output buffer
     int64_t hash_cap;    // record capacity of the clip
     int64_t stft_base;   // first K1 wave-strip of the clip
+    int64_t flag_base;   // first row-flag word of the clip's first K2 strip
+    int64_t strip_len;   // K2 strip length of the clip's group (the flags are indexed by strip)
 };
 
 }  // namespace aid

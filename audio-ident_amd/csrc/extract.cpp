@@ -29,6 +29,7 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
     HIP_TRY(x.desc.reserve((size_t)n_clips + 1));
     HIP_TRY(x.power.reserve((size_t)plane * kBins));
     HIP_TRY(x.mask.reserve((size_t)p.total_frames * kMaskWords));
+    HIP_TRY(x.rowflags.reserve((size_t)p.flag_words + 4));
     HIP_TRY(x.hotw.reserve((size_t)p.total_frames + 1));
     // relative mode: the clips' maxima start at +0 on this call's stream, ahead of the first group's K1
     if (rel) {
@@ -88,19 +89,20 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
             {
                 ProfScope ps(e, AID_K_PEAKS, s, true);
                 launch_peak_pick(p.width, x.power.p, x.desc.p + g.first, g.n, g.frame0, g.strips, g.strip_len,
-                                 e->cfg.peak_threshold, x.hotw.p, x.mask.p, x.k2_cold.p, qmax, e->cfg.peak_rel, s);
+                                 e->cfg.peak_threshold, x.hotw.p, x.mask.p, x.k2_cold.p, qmax, e->cfg.peak_rel,
+                                 x.rowflags.p, s);
             }
         }
         if (p.multi_chunk) {  // some clip spans several K3 chunks: their bases need the COUNT pass
             ProfScope ps(e, AID_K_LANDMARK_COUNT, s, true);
-            launch_landmarks(x.mask.p, x.desc.p, n_clips, p.chunks, x.chunk_counts.p, x.records.p, x.counts.p, false,
-                             nullptr, nullptr, 0u, 0u, p.one_chunk_each, s);
+            launch_landmarks(x.mask.p, x.rowflags.p, x.desc.p, n_clips, p.chunks, x.chunk_counts.p, x.records.p,
+                             x.counts.p, false, nullptr, nullptr, 0u, 0u, p.one_chunk_each, s);
         }
         {
             ProfScope ps(e, AID_K_LANDMARK_WRITE, s, true);
-            launch_landmarks(x.mask.p, x.desc.p, n_clips, p.chunks, x.chunk_counts.p, x.records.p, x.counts.p, true,
-                             x.h_cold_dev ? x.k2_cold.p : nullptr, x.h_cold_dev, (uint32_t)(p.width * p.strips),
-                             (uint32_t)p.strips, p.one_chunk_each, s);
+            launch_landmarks(x.mask.p, x.rowflags.p, x.desc.p, n_clips, p.chunks, x.chunk_counts.p, x.records.p,
+                             x.counts.p, true, x.h_cold_dev ? x.k2_cold.p : nullptr, x.h_cold_dev,
+                             (uint32_t)(p.width * p.strips), (uint32_t)p.strips, p.one_chunk_each, s);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -215,7 +217,21 @@ int aid_result_thresholds(aid_engine *e, float *out) {
 
 int aid_result_peakmask(aid_engine *e, int32_t clip, uint64_t *out, int64_t cap) {
     if (int rc = result_ready(e, &clip)) return rc;
-    return read_rows(e, clip, e->ext.mask.p, kMaskWords, out, cap);
+    if (int rc = read_rows(e, clip, e->ext.mask.p, kMaskWords, out, cap)) return rc;
+    // K2 stores a row's 4 words of a 256-bin quarter only when they hold a peak (aidfp_layout.h, row flags): the
+    // complete mask has zeros wherever the quarter's flag is clear
+    const ClipDesc &d = e->ext.plan.desc[clip];
+    if (d.frames == 0) return AID_OK;
+    const int64_t L = d.strip_len, per = flag_words_per_strip((int)L);
+    std::vector<uint32_t> fl((size_t)(((d.frames + L - 1) / L) * per));
+    HIP_TRY(hipMemcpy(fl.data(), e->ext.rowflags.p + d.flag_base, fl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < d.frames; ++r) {
+        const int64_t o = r % L;
+        const uint32_t *unit = fl.data() + (r / L) * per + 4 * (o >> 5);
+        for (int q = 0; q < 4; ++q)
+            if (!((unit[q] >> (o & 31)) & 1u)) std::memset(out + r * kMaskWords + 4 * q, 0, 4 * sizeof(uint64_t));
+    }
+    return AID_OK;
 }
 
 int aid_spectrogram(aid_engine *e, const float *pcm, int64_t n, float *out, int64_t cap) {

@@ -5,8 +5,9 @@
 // a3; reference call sites fingerprint.py:117-125, 185-193).
 //
 // Unit = (clip, chunk of kHashChunk anchor frames). A workgroup:
-//   1. popcounts the 16 mask words of every frame in [c0, min(c1+63, F)) and
-//      block-scans the counts (frame -> first peak index);
+//   1. popcounts the mask words of every frame in [c0, min(c1+63, F)), of the
+//      quarters K2 flagged only (row flags, aidfp_layout.h: the others were not
+//      written), and block-scans the counts (frame -> first peak index);
 //   2. expands the masks into an LDS peak list packed (frame << 10 | bin), which
 //      is already in (t, k) order -- exactly the target order of FPSPEC 6;
 //   3. gives each thread a contiguous run of anchors; a thread walks forward from
@@ -52,8 +53,10 @@ __device__ __forceinline__ uint32_t make_hash(int k1, int k2, int dt) {
 }
 
 template <bool WRITE>
-__global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ mask, const ClipDesc *__restrict__ clips,
-                                                  int n_clips, int64_t total_chunks, int64_t *__restrict__ chunk_counts,
+__global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ mask,
+                                                  const uint32_t *__restrict__ rowflags,
+                                                  const ClipDesc *__restrict__ clips, int n_clips,
+                                                  int64_t total_chunks, int64_t *__restrict__ chunk_counts,
                                                   uint64_t *__restrict__ records, int64_t *__restrict__ clip_counts,
                                                   uint32_t *__restrict__ k2_cold, uint64_t *__restrict__ k2_cold_host,
                                                   uint32_t k2_waves, uint32_t k2_strips, int one_chunk_each) {
@@ -98,36 +101,64 @@ __global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ 
     const int64_t nck = (F + kHashChunk - 1) / kHashChunk;
     if (!WRITE && nck == 1) return;  // single-chunk clips: the WRITE pass needs no base
 
-    // 1. per-frame counts over a contiguous run of frames per thread, block scan
+    // 1. per-frame counts, then their sums over a contiguous run of frames per thread, block scan
     const int per = (nf + kK3 - 1) / kK3;
     const int fa = min(tid * per, nf), fz = min(fa + per, nf);
     int64_t mine = 0;
-    for (int f = fa; f < fz; ++f) {
+    // K2's row flags (aidfp_layout.h) say which 256-bin quarters of a frame hold a peak: only their 4 mask words are
+    // read; K2 does not write the others (stale memory). Frame fr of the clip is row o of its strip st; the 16-byte
+    // unit of word o >> 5 holds bit o & 31 of the four quarters.
+    // Frames tid, tid + kK3, ... here (neighbouring lanes read neighbouring rows, and a thread's flag loads are all
+    // in flight before the mask loads that depend on them); the contiguous runs below then sum from LDS
+    const uint32_t L = (uint32_t)cd.strip_len;
+    const uint32_t *FLc = rowflags + cd.flag_base;
+    const int64_t fnw = flag_words_per_strip((int)L);
+    constexpr int kP1 = (kHashChunk + kZoneDT + kK3 - 1) / kK3;  // frames per thread at most
+    uint32_t nibs[kP1];
+#pragma unroll
+    for (int i = 0; i < kP1; ++i) {
+        const int f = tid + i * kK3;
+        nibs[i] = 0;
+        if (f < nf) {
+            const uint32_t fr = (uint32_t)(c0 + f), st = fr / L, o = fr - st * L;  // a clip's rows fit 32 bits
+            const uint4 fu = *reinterpret_cast<const uint4 *>(FLc + st * fnw + 4 * (o >> 5));
+            nibs[i] = ((fu.x >> (o & 31)) & 1u) | ((fu.y >> (o & 31)) & 1u) << 1 | ((fu.z >> (o & 31)) & 1u) << 2 |
+                      ((fu.w >> (o & 31)) & 1u) << 3;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kP1; ++i) {
+        const int f = tid + i * kK3;
+        if (f >= nf) continue;
         uint32_t c = 0;
 #pragma unroll
-        for (int w = 0; w < kMaskWords; ++w) c += __popcll(Mc[f * kMaskWords + w]);
-        foff[f] = c;
-        mine += c;
+        for (int b = 0; b < 4; ++b) {
+            if (!((nibs[i] >> b) & 1u)) continue;
+#pragma unroll
+            for (int w = 4 * b; w < 4 * b + 4; ++w) c += __popcll(Mc[f * kMaskWords + w]);
+        }
+        foff[f] = c | nibs[i] << 28;  // c <= 64 (no two peaks within +-15 bins)
     }
+    __syncthreads();
+    for (int f = fa; f < fz; ++f) mine += foff[f] & 0x0FFFFFFFu;
     int64_t npk = 0;
     int64_t run = block_excl_scan(mine, scan_tmp, &npk);
     // 2. expand to the (t,k)-ordered peak list
     for (int f = fa; f < fz; ++f) {
-        const uint32_t c = foff[f];
+        const uint32_t c = foff[f] & 0x0FFFFFFFu, nib = foff[f] >> 28;
         foff[f] = (uint32_t)run;
         // most frames hold no peak (~0.35 per frame at the bench config): skip their mask reload
         if (c == 0) continue;
         int64_t idx = run;
-        uint64_t W[kMaskWords];
-#pragma unroll
-        for (int w = 0; w < kMaskWords; ++w) W[w] = Mc[f * kMaskWords + w];
         // no unshuffle: a 4-bin group holds at most one peak (FPSPEC 5: no two peaks within +-15 bins), so the
         // OR of a 256-bin block's 4 ballot words has one bit per peak, in ascending bin order; the word
         // holding that bit gives the bin's offset i in the group (bin = 256 b + 4 l + i)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            const uint64_t w1 = W[4 * b + 1], w2 = W[4 * b + 2], w3 = W[4 * b + 3];
-            for (uint64_t m = W[4 * b] | w1 | w2 | w3; m; m &= m - 1) {
+            if (!((nib >> b) & 1u)) continue;  // an unflagged quarter holds no peak (and its words are stale)
+            const uint64_t *Wb = Mc + f * kMaskWords + 4 * b;
+            const uint64_t w0 = Wb[0], w1 = Wb[1], w2 = Wb[2], w3 = Wb[3];
+            for (uint64_t m = w0 | w1 | w2 | w3; m; m &= m - 1) {
                 const int l = __ffsll((unsigned long long)m) - 1;
                 const int i = (int)((w1 >> l) & 1) + 2 * (int)((w2 >> l) & 1) + 3 * (int)((w3 >> l) & 1);
                 plist[idx++] = ((uint32_t)f << 10) | (uint32_t)(256 * b + 4 * l + i);
@@ -220,17 +251,17 @@ __global__ __launch_bounds__(kK3) void k_landmarks(const uint64_t *__restrict__ 
     }
 }
 
-void launch_landmarks(const uint64_t *mask, const ClipDesc *clips, int n_clips, int64_t total_chunks,
-                      int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write, uint32_t *k2_cold,
-                      uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips, bool one_chunk_each,
-                      hipStream_t s) {
+void launch_landmarks(const uint64_t *mask, const uint32_t *rowflags, const ClipDesc *clips, int n_clips,
+                      int64_t total_chunks, int64_t *chunk_counts, uint64_t *records, int64_t *clip_counts, bool write,
+                      uint32_t *k2_cold, uint64_t *k2_cold_host, uint32_t k2_waves, uint32_t k2_strips,
+                      bool one_chunk_each, hipStream_t s) {
     if (total_chunks <= 0) return;
     if (write)
-        timed_launch(k_landmarks<true>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, clips, n_clips,
+        timed_launch(k_landmarks<true>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, rowflags, clips, n_clips,
                            total_chunks, chunk_counts, records, clip_counts, k2_cold, k2_cold_host, k2_waves,
                      k2_strips, one_chunk_each ? 1 : 0);
     else
-        timed_launch(k_landmarks<false>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, clips, n_clips,
+        timed_launch(k_landmarks<false>, dim3((unsigned)total_chunks), dim3(kK3), 0, s, mask, rowflags, clips, n_clips,
                            total_chunks, chunk_counts, records, clip_counts, (uint32_t *)nullptr, (uint64_t *)nullptr, 0u,
                      0u, one_chunk_each ? 1 : 0);
 }

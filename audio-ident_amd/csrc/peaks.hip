@@ -23,7 +23,8 @@
 //     word 4*w + i of a frame holds, at bit l, the peak flag of bin 256*w + 4*l + i
 //     ("ballot layout"; K3 and aidfp.engine.peaks_from_mask unshuffle it).
 // Only hot 16-bin chunks (K1's per-row hot word, aidfp_layout.h hot_bit) are loaded; a wave whose
-// window chunks are cold in every row of its strip exits at once (it only writes zero mask words).
+// window chunks are cold in every row of its strip exits at once (it only writes its zero row flags: a row's mask
+// words of a quarter are stored only when they hold a peak, aidfp_layout.h).
 // Strips are dealt to workgroups XCD-aware so neighbouring strips (which share
 // halo rows) run on the same XCD's L2. The variants measured against this layout
 //  live in the git history (commit c236449, the AID_K2_* switches).
@@ -33,7 +34,7 @@
 // quarter waves of a 4-wave workgroup only exit, but the workgroup still needs a wave slot on every SIMD and the LDS
 // of 1024 bins to start. When some chunk the upper quarters' windows see is hot in a row of the strip, the same
 // workgroup walks the strip a second time over bins 512..1023 (same code, ring state re-initialised); otherwise it
-// writes their zero mask words. The 16 bins past the group's edge (chunk 32 for the lower group, 31 for the upper)
+// writes their zero row flags. The 16 bins past the group's edge (chunk 32 for the lower group, 31 for the upper)
 // are staged into the row pads only when that chunk is hot somewhere in the strip.
 #include "aidfp_device.h"
 #include "aidfp_launch.h"
@@ -85,6 +86,7 @@ struct PeakPickArgs {
     uint32_t *cold_cnt;
     const uint32_t *clip_qmax;
     float rel;
+    uint32_t *rowflags;
 };
 
 // occupancy 4 forced by the launch bounds (<= 128 VGPRs, no spills)
@@ -98,7 +100,8 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
                                                   int n_clips_, int64_t f0_, int64_t total_strips_, int strip_len_, float thr_,
                                                   const uint64_t *__restrict__ hot_, uint64_t *__restrict__ mask_,
                                                   uint32_t *__restrict__ cold_cnt_,
-                                                  const uint32_t *__restrict__ clip_qmax_, float rel_) {
+                                                  const uint32_t *__restrict__ clip_qmax_, float rel_,
+                                                  uint32_t *__restrict__ rowflags_) {
     static_assert(W == 2 || W == 4, "quarter waves per workgroup");
     constexpr int kGB = 256 * W;  // bins of a workgroup's column group
     __shared__ __attribute__((aligned(16))) int rows[kRowsPerStep][kGB + 32];  // keys, 16 pads each side
@@ -119,13 +122,14 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
         uint64_t *mask = mask_;
         uint32_t *cold_cnt = cold_cnt_;
         const uint32_t *clip_qmax = clip_qmax_;
+        uint32_t *rowflags = rowflags_;
         if (g > 0) {
             typedef const __attribute__((address_space(4))) PeakPickArgs *ArgPtr;  // scalar loads
             ArgPtr a = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(a));
             power = a->power, clips = a->clips, n_clips = a->n_clips, f0 = a->f0, total_strips = a->total_strips;
             strip_len = a->strip_len, thr = a->thr, hot = a->hot, mask = a->mask, cold_cnt = a->cold_cnt;
-            clip_qmax = a->clip_qmax, rel = a->rel;
+            clip_qmax = a->clip_qmax, rel = a->rel, rowflags = a->rowflags;
             __syncthreads();  // every wave is done with the first walk's last rows
         }
         // wl = the 256-bin quarter of the group this wave owns, rotated by the workgroup index: the
@@ -163,6 +167,19 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
         const int t1 = min(t0 + strip_len, F);
         const float *P = power + (fb - f0) * kBins;  // the plane holds rows from absolute frame f0 on
         uint64_t *M = mask + fb * kMaskWords + 4 * wave + lane;  // lanes 0..3 store ballot words
+        // Row flags of the strip (aidfp_layout.h): word j of quarter q at FL[4 j + q], bit b = row t0 + 32 j + b has a
+        // peak in quarter q. Only such rows get their 4 mask words of the quarter stored: the others' words keep what
+        // an earlier call left, and K3 and the mask reader go by the flags. A wave owns the words of its quarter(s)
+        // and writes all nw of them, also those past a clip's last row (plain stores, nothing to clear beforehand)
+        const int nw = (strip_len + 31) >> 5;
+        uint32_t *FL = rowflags + clips[lo].flag_base + (strip - clips[lo].strip_base) * (4 * nw);
+        auto no_peaks = [&](int q) {  // quarter q of the strip holds no peak
+#if defined(AID_K2_EMIT_ALL)
+            uint64_t *Mz = mask + fb * kMaskWords + 4 * q + (lane & 3);
+            for (int r = t0 + (lane >> 2); r < t1; r += 16) Mz[(int64_t)r * kMaskWords] = 0;
+#endif
+            for (int j = lane; j < nw; j += 64) FL[4 * j + q] = 0u;
+        };
         // K1's plane holds Q = 4P (stft.hip, real split): compare against 4 thr (exact: thr <= 2^100)
         int kthr = __float_as_int(4.0f * thr);                  // thr > 0 (engine config check)
         // FPSPEC 5.1 (clip_qmax set): 4 thr_c = max(4 thr, rel * Qmax_c), Qmax_c = K1's maximum over the clip's whole
@@ -246,8 +263,8 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
         bool need2 = false, bhot = false;
         {
             // strip-cold wave: if those blocks are cold in every row the strip reads, every key this wave
-            // stages or compares is 0, so it has no candidate and its mask words are 0 (exact, as the
-            // per-row cold skip). It writes those zeros, zeroes its staged bins once (the neighbouring
+            // stages or compares is 0, so it has no candidate and its quarter holds no peak (exact, as the
+            // per-row cold skip). It writes the quarter's zero row flags, zeroes its staged bins once (the neighbouring
             // waves' windows read them), and only keeps the workgroup's barrier count (2 per 4 rows)
             uint64_t acc = 0;
             for (int r = rbeg + lane; r < rbeg + iters; r += 64) acc |= (r >= 0 && r < F) ? HW[r] : 0ull;
@@ -255,15 +272,14 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
             if (W < 4) {
                 bhot = __ballot((acc >> hot_bit(g == 0 ? 16 * W : 16 * W - 1)) & 1ull) != 0;
                 if (g == 0) {
-                    // chunks 16W-1 .. 63: all that the quarters above the group see. Cold in every row: their mask
-                    // words are zeros (wave wl writes those of quarter W + wl). Else no wave leaves before the
+                    // chunks 16W-1 .. 63: all that the quarters above the group see. Cold in every row: they hold no
+                    // peak (wave wl writes the zero row flags of quarter W + wl). Else no wave leaves before the
                     // second walk: a strip-cold one runs the rows' all-cold path
                     uint64_t up = 0;
                     for (int c = 16 * W - 1; c < 64; ++c) up |= 1ull << hot_bit(c);
                     need2 = __ballot((acc & up) != 0ull) != 0;
                     if (!need2) {
-                        uint64_t *Mz = mask + fb * kMaskWords + 4 * (W + wl) + (lane & 3);
-                        for (int r = t0 + (lane >> 2); r < t1; r += 16) Mz[(int64_t)r * kMaskWords] = 0;
+                        no_peaks(W + wl);
                     } else {
                         cold = false;
                         // counted like the cold waves (counters 64..127, read and reset by K3): the host's width choice
@@ -277,8 +293,7 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
                     reinterpret_cast<int4 *>(&rows[j][16])[lt] = make_int4(0, 0, 0, 0);
                     bms[j][4 + lt] = 0;
                 }
-                uint64_t *Mz = mask + fb * kMaskWords + 4 * wave + (lane & 3);
-                for (int r = t0 + (lane >> 2); r < t1; r += 16) Mz[(int64_t)r * kMaskWords] = 0;
+                no_peaks(wave);
                 // the wave terminates: s_barrier waits only for a workgroup's surviving waves, and its
                 // registers go to waves of workgroups still waiting for a slot (host: extract_locked); its
                 // zeroed LDS bins are written before it ends. The cold waves are counted (64 counters, read
@@ -330,6 +345,7 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
         for (int j = 0; j < kRowsPerStep; ++j) hsave[j] = hcur[j] = hotword(rbeg + j);
 #endif
 
+        uint32_t fw = 0u;  // the flag word being filled (uniform: a scalar register)
         for (int base = 0; base < iters; base += 8) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
@@ -466,8 +482,24 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
                 }
                 }
                 const uint64_t b0 = bal[0], b1 = bal[1], b2 = bal[2], b3 = bal[3];
+                // the decided row rd = r - 7 = t0 + it - 14. A ballot bit needs a candidate, and only the strip's
+                // output rows have any (thr_row; pend starts empty): nz implies t0 <= rd < t1, one scalar test for both
                 const int rd = r - kPeakDT;
-                if (rd >= t0 && rd < t1) {
+#if defined(AID_K2_NOEMIT)
+                asm volatile("" ::"s"(b0), "s"(b1), "s"(b2), "s"(b3));  // the decisions are still made
+                const bool nz = false;
+#else
+                const uint64_t ball = b0 | b1 | b2 | b3;
+                const bool nz = ball != 0ull;
+                // the flag bit as a 32-bit scalar (bit count, capped at 1): a bool kept across the branch below is a
+                // lane mask to hipcc, and the flag word then lives in a vector register (4 VALU per row)
+                fw |= min((uint32_t)__builtin_popcountll(ball), 1u) << ((it - 2 * kPeakDT) & 31);
+#endif
+#if defined(AID_K2_EMIT_ALL)
+                if (it >= 2 * kPeakDT) {
+#else
+                if (nz) {
+#endif
                     // lane i < 4 stores ballot word i: 8 v_writelane of the SGPR ballots
                     uint32_t lo, hi;  // no zero init (2 VALU per row): only lanes 0..3 are stored
                     asm volatile("" : "=v"(lo), "=v"(hi));
@@ -481,7 +513,19 @@ __global__ __launch_bounds__(64 * W, 4) void k_peak_pick(
                     hi = write_lane<3>(hi, (uint32_t)(b3 >> 32));
                     if (lane < 4) M[(int64_t)rd * kMaskWords] = ((uint64_t)hi << 32) | lo;
                 }
+                // a full flag word: strip row it - 14 = 31 mod 32, that is slot 5 of every fourth round of the unroll
+                // (it = 13 is row -1: no word of this strip)
+                if (s == (2 * kPeakDT + 31) % 8 && it > 2 * kPeakDT && ((it - 2 * kPeakDT) & 31) == 31) {
+                    if (lane == 0) FL[((it - 2 * kPeakDT) >> 5) * 4 + wave] = fw;
+                    fw = 0u;
+                }
             }
+        }
+        // the strip's last, partial word (its bits past the last row are 0), then the words past a clip's last row
+        {
+            const int nr = t1 - t0;
+            if (lane == 0 && (nr & 31)) FL[(nr >> 5) * 4 + wave] = fw;
+            for (int j = ((nr + 31) >> 5) + lane; j < nw; j += 64) FL[4 * j + wave] = 0u;
         }
 #if defined(AID_K2_STAMPS)
         {
@@ -512,17 +556,20 @@ int k2_stamps_read(unsigned long long *out, bool reset) {
 // power holds the rows from absolute frame f0 on (a group of the call's clips, extract_locked); the clips' strip_base
 // count from 0 within the group. clip_qmax (FPSPEC 5.1): null = the absolute threshold thr alone; else the group's
 // words of K1's per-clip max Q, and every clip's threshold is max(thr, rel * its max P). width = quarter waves per
-// workgroup (2 or 4); cold_cnt holds 128 counters: 0..63 strip-cold waves, 64..127 strips walked twice (width 2)
+// workgroup (2 or 4); cold_cnt holds 128 counters: 0..63 strip-cold waves, 64..127 strips walked twice (width 2).
+// rowflags: the call's flag words (the clips' flag_base count over the call); mask rows without a flag are not written.
+// Timing-only diagnostic builds (results wrong or the old traffic; never the product): AID_K2_NOEMIT compiles the mask
+// emission out (every flag 0), AID_K2_EMIT_ALL writes the flags and every mask word as before the flags existed
 void launch_peak_pick(int width, const float *power, const ClipDesc *clips, int n_clips, int64_t f0, int64_t total_strips,
                       int strip_len, float thr, const uint64_t *hot, uint64_t *mask, uint32_t *cold_cnt,
-                      const uint32_t *clip_qmax, float rel, hipStream_t s) {
+                      const uint32_t *clip_qmax, float rel, uint32_t *rowflags, hipStream_t s) {
     if (total_strips <= 0) return;
     if (width == 2)
         timed_launch(k_peak_pick<2>, dim3((unsigned)total_strips), dim3(128), 0, s, power, clips, n_clips, f0,
-                     total_strips, strip_len, thr, hot, mask, cold_cnt, clip_qmax, rel);
+                     total_strips, strip_len, thr, hot, mask, cold_cnt, clip_qmax, rel, rowflags);
     else
         timed_launch(k_peak_pick<4>, dim3((unsigned)total_strips), dim3(256), 0, s, power, clips, n_clips, f0,
-                     total_strips, strip_len, thr, hot, mask, cold_cnt, clip_qmax, rel);
+                     total_strips, strip_len, thr, hot, mask, cold_cnt, clip_qmax, rel, rowflags);
 }
 
 // resident K2 workgroups per CU (registers / LDS) at a width, for sizing strips to one round
