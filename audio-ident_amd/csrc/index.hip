@@ -90,7 +90,7 @@ __global__ void k_index_scatter(const uint32_t *__restrict__ ph, const uint32_t 
     }
 }
 
-// exclusive scan of n u32 counts (n = k * 1024) -> out; block sums -> bsum
+// exclusive scan of n u32 counts, 1024 per block (a partial last block reads zeros) -> out; block sums -> bsum
 __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
                                                      uint32_t *__restrict__ bsum, int64_t n) {
     __shared__ uint32_t s[1024];
@@ -1051,13 +1051,17 @@ void launch_index_scatter(const uint32_t *ph, const uint32_t *ptrack, const uint
                        cursor, post);
 }
 
-// exclusive scan of n counts (n multiple of 1024); tmp holds >= 2 * ceil(n/1024) + 1024 u32
+// exclusive scan of n counts, any n >= 1 (the kernels guard the partial last block: the CSR build scans 2^26 + 1
+// keys, the compaction any number of blocks). Each level with more than one block takes 2 * ceil(n / 1024) u32 of
+// tmp (block sums, their offsets) and hands the rest to the scan of its block sums; the last level takes 1. So tmp
+// holds >= 2 * ceil(n / 2^10) + 2 * ceil(n / 2^20) + 2 * ceil(n / 2^30) + 1 u32 (the callers reserve
+// 4 * (n / 1024 + 2) + 4096)
 void launch_scan(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *tmp, hipStream_t s) {
     const int64_t nb = (n + 1023) / 1024;
     uint32_t *bsum = tmp, *boff = tmp + nb, *b2 = tmp + 2 * nb;
     hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nb), dim3(1024), 0, s, in, out, bsum, n);
     if (nb > 1) {
-        // recursive on block sums (nb <= 2^16 for 2^26 keys -> at most two levels)
+        // recursive on block sums (nb = 2^16 + 1 for the 2^26 + 1 keys: three levels, the last of one block)
         launch_scan(bsum, boff, nb, b2, s);
         hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(1024), 0, s, out, boff, n);
     }

@@ -10,6 +10,7 @@ import pytest
 import k5_fixtures as F
 import oracle as O
 from aidfp.engine import Engine
+from store_ref import csr_mirror
 
 pytestmark = pytest.mark.gpu
 SR = 16000
@@ -40,16 +41,6 @@ def add(eng, post):
     if len(post):
         h, tr, t = F.columns(post)
         eng.index_add_postings(h.ctypes.data, tr.ctypes.data, t.ctypes.data, len(post), device=False)
-
-
-def csr_mirror(post, removed=()):
-    p = post[~np.isin(post[:, 1], np.asarray(list(removed), dtype=np.uint32))]
-    keys = F.bucket_key(p[:, 0])
-    order = np.argsort(keys, kind="stable")
-    posts = p[order, 1].astype(np.uint64) | (p[order, 2].astype(np.uint64) << np.uint64(32))
-    offs = np.zeros(KEYS + 1, np.uint32)
-    offs[1:] = np.cumsum(np.bincount(keys, minlength=KEYS)).astype(np.uint32)
-    return offs, posts
 
 
 def check_csr(eng, post, removed=()):

@@ -17,6 +17,7 @@ import oracle as O
 from aidfp import synth
 from aidfp._lib import AID_ERR_STATE, EngineError
 from aidfp.engine import Engine
+from store_ref import csr_mirror  # the CSR K4 must build: live postings stably sorted by bucket key
 
 pytestmark = pytest.mark.gpu
 SR = 16000
@@ -308,21 +309,6 @@ def test_removal_while_live():
 
 
 # ---------------------------------------------------------------- 5. cap and fold
-def _bucket_key(h):
-    return F.bucket_key(h)
-
-
-def csr_mirror(post, removed=()):
-    """The CSR K4 must build (tests/test_gpu_match.py _csr_mirror): live postings stably sorted by bucket key."""
-    p = post[~np.isin(post[:, 1], np.asarray(list(removed), dtype=np.uint32))]
-    keys = _bucket_key(p[:, 0])
-    order = np.argsort(keys, kind="stable")
-    posts = p[order, 1].astype(np.uint64) | (p[order, 2].astype(np.uint64) << np.uint64(32))
-    offs = np.zeros((1 << 26) + 1, np.uint32)
-    offs[1:] = np.cumsum(np.bincount(keys, minlength=1 << 26)).astype(np.uint32)
-    return offs, posts
-
-
 def test_cap_and_fold(audio):
     recs, clips, src = audio
     cap = 3000

@@ -8,6 +8,7 @@ import pytest
 import oracle as O
 from aidfp import synth
 from aidfp.engine import Engine
+from store_ref import csr_mirror as _csr_mirror  # the CSR K4 must build: the stable key sort of the live postings
 
 pytestmark = pytest.mark.gpu
 SR = 44100
@@ -329,27 +330,6 @@ def test_sort_build_many_column_groups(removed):
     gone = {int(tracks[i]) for i in pick[:5]} if removed else set()
     assert sum(h == int(tracks[i]) for h, i in zip(hits, pick) if int(tracks[i]) not in gone) >= 40
     assert not any(h in gone for h in hits if h is not None)
-
-
-def _bucket_key_np(h):
-    """Host mirror of aidfp_layout.h bucket_key (the CSR's key permutation of the 26 hash bits)."""
-    h = h.astype(np.uint32)
-    return ((((h >> 22) & 0xFF) << 18) | ((h >> 30) << 16) | (((h >> 12) & 0x7F) << 9) | (((h >> 19) & 0x7) << 6) |
-            (h & 0x3F)).astype(np.uint32)
-
-
-def _csr_mirror(post, removed):
-    """The CSR K4 must build from stored postings [n, 3] (hash, track, t): live postings stably sorted by bucket key
-    (a bucket keeps arrival order), values track | t << 32, offsets[k] = live postings with key < k."""
-    live = ~np.isin(post[:, 1], np.asarray(list(removed), dtype=np.uint32))
-    p = post[live]
-    keys = _bucket_key_np(p[:, 0])
-    order = np.argsort(keys, kind="stable")
-    posts = p[order, 1].astype(np.uint64) | (p[order, 2].astype(np.uint64) << np.uint64(32))
-    counts = np.bincount(keys, minlength=1 << 26)
-    offs = np.zeros((1 << 26) + 1, np.uint32)
-    offs[1:] = np.cumsum(counts).astype(np.uint32)
-    return offs, posts
 
 
 @pytest.mark.parametrize("mode", ["sort", "ballot"])
