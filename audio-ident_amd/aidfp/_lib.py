@@ -104,6 +104,19 @@ class AidVibeRow(ctypes.Structure):
     ]
 
 
+AID_VEC_MAX_EXCLUDE = 8
+
+
+class AidVecFilter(ctypes.Structure):
+    _fields_ = [
+        ("any_of", ctypes.c_uint64),
+        ("all_of", ctypes.c_uint64),
+        ("none_of", ctypes.c_uint64),
+        ("n_exclude", ctypes.c_uint32),
+        ("exclude", ctypes.c_uint32 * AID_VEC_MAX_EXCLUDE),
+    ]
+
+
 class AidMelChunk(ctypes.Structure):
     _fields_ = [
         ("clip", ctypes.c_int32),
@@ -207,6 +220,11 @@ SIGNATURES = [
     ("aid_vec_prefilter", ctypes.c_int, [P, I32, I32]),
     ("aid_vec_scores_i8", ctypes.c_int, [P, P, I32, I32, P, P, I64]),
     ("aid_vec_prefilter_stats", ctypes.c_int, [P, P, I32, I32]),
+    ("aid_vec_add_tagged", ctypes.c_int, [P, P, P, P, P, P, I64, I32]),
+    ("aid_vec_retag", ctypes.c_int, [P, ctypes.c_uint32, ctypes.c_uint64]),
+    ("aid_vec_tags", ctypes.c_int, [P, P, I64]),
+    ("aid_vec_search_filtered", ctypes.c_int, [P, P, I32, I32, I32, P, P, P, P]),
+    ("aid_vibe_lane_filtered", ctypes.c_int, [P, P, I32, I32, I32, I32, ctypes.c_double, P, P, ctypes.c_double, I32, P, P, P]),
     ("aid_mel_configure", ctypes.c_int, [P, I32, ctypes.c_double, ctypes.c_double, P]),
     ("aid_mel_filters", ctypes.c_int, [P, P]),
     ("aid_mel_plan", ctypes.c_int, [P, I32, I32, I64, P, P, I64]),

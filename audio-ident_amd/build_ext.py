@@ -21,7 +21,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["stft.hip", "peaks.hip", "landmarks.hip", "synth.hip", "index.hip", "index_sort.hip", "index_merge.hip", "stream.hip",
-           "resample.hip", "dedup.hip", "exact.hip", "vector.hip", "vector_q8.hip", "mel.hip", "chroma.hip", "engine.cpp", "extract.cpp",
+           "resample.hip", "dedup.hip", "exact.hip", "vector.hip", "vector_q8.hip", "vector_filter.hip", "mel.hip", "chroma.hip", "engine.cpp", "extract.cpp",
            "index_host.cpp", "index_exchange.cpp", "query.cpp", "speed.cpp", "mel.cpp", "chroma.cpp"]
 FLAGS = [
     f"--offload-arch={ARCH}",

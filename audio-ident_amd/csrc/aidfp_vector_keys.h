@@ -23,6 +23,24 @@ __device__ __forceinline__ float vec_key_score(unsigned long long key) {
 }
 __device__ __forceinline__ uint32_t vec_key_entry(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
 
+// Which entries a selection kernel may pick for query q: the compile-time parameter of k_vec_select,
+// k_vec_slice_max, k_vec_filter and k_vec_filter_q8. VecLive is FPSPEC 9's "live" (the tombstone column; one pointer,
+// so the kernels' arguments are what they were); VecAllowed is FPSPEC 9.2's "passes": bit e of the allow-bitmap
+// fmap[q] that k_vec_allow wrote. A lane reads the 32-bit word e >> 5, so the 64 consecutive entries of a wave
+// come from two or three adjacent words, one coalesced load, wherever the slice starts.
+struct VecLive {
+    const uint8_t *dead;
+    __device__ __forceinline__ const uint8_t *row(int) const { return dead; }
+    static __device__ __forceinline__ bool test(const uint8_t *r, int64_t e) { return !r[e]; }
+};
+struct VecAllowed {
+    const uint32_t *bm;   // [bitmaps][words32]
+    const int32_t *fmap;  // query of the launch -> bitmap
+    int64_t words32;
+    __device__ __forceinline__ const uint32_t *row(int q) const { return bm + (size_t)fmap[q] * words32; }
+    static __device__ __forceinline__ bool test(const uint32_t *r, int64_t e) { return (r[e >> 5] >> (e & 31)) & 1u; }
+};
+
 // Bitonic sort, descending, of sp (a power of two) keys in LDS by a 256-thread workgroup.
 template <typename T>
 __device__ __forceinline__ void vec_sort_desc(T *keys, int sp) {

@@ -584,8 +584,17 @@ int aid_vec_reset(aid_engine *e, int32_t dim) { VEC_CALL(e, nullptr, vec_reset(e
 
 int aid_vec_add(aid_engine *e, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index,
                 const double *offset_sec, int64_t n, int32_t location) {
-    VEC_CALL(e, nullptr, vec_add(e->vec, vecs, tracks, chunk_index, offset_sec, n, location, s));
+    VEC_CALL(e, nullptr, vec_add(e->vec, vecs, tracks, chunk_index, offset_sec, nullptr, n, location, s));
 }
+
+int aid_vec_add_tagged(aid_engine *e, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index,
+                       const double *offset_sec, const uint64_t *tags, int64_t n, int32_t location) {
+    VEC_CALL(e, nullptr, vec_add(e->vec, vecs, tracks, chunk_index, offset_sec, tags, n, location, s));
+}
+
+int aid_vec_retag(aid_engine *e, uint32_t track, uint64_t tags) { VEC_CALL(e, nullptr, vec_retag(e->vec, track, tags)); }
+
+int aid_vec_tags(aid_engine *e, uint64_t *out, int64_t cap) { VEC_CALL(e, nullptr, vec_tags(e->vec, out, cap)); }
 
 int aid_vec_remove(aid_engine *e, uint32_t track) { VEC_CALL(e, nullptr, vec_remove(e->vec, track, s)); }
 
@@ -602,7 +611,12 @@ int aid_vec_count(aid_engine *e, int64_t *n_entries, int64_t *n_live, int32_t *d
 
 int aid_vec_search(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
                    aid_vec_hit *hits, int32_t *n_hits, void *stream) {
-    VEC_CALL(e, stream, vec_search(e->vec, queries, nq, location, limit, hits, n_hits, s));
+    VEC_CALL(e, stream, vec_search(e->vec, queries, nq, location, limit, nullptr, hits, n_hits, s));
+}
+
+int aid_vec_search_filtered(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                            const aid_vec_filter *filters, aid_vec_hit *hits, int32_t *n_hits, void *stream) {
+    VEC_CALL(e, stream, vec_search(e->vec, queries, nq, location, limit, filters, hits, n_hits, s));
 }
 
 int aid_vec_scores(aid_engine *e, const float *queries, int32_t nq, int32_t location, float *out, int64_t cap) {
@@ -619,7 +633,15 @@ int aid_vec_aggregate(aid_engine *e, const aid_vec_hit *hits, const int64_t *hof
 int aid_vibe_lane(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
                   int32_t top_k_per_track, double diversity_weight, const uint32_t *exclude, double threshold,
                   int32_t max_out, aid_vibe_row *out, int32_t *n_out, void *stream) {
-    VEC_CALL(e, stream, vec_lane(e->vec, queries, nq, location, limit, top_k_per_track, diversity_weight, exclude,
+    VEC_CALL(e, stream, vec_lane(e->vec, queries, nq, location, limit, top_k_per_track, diversity_weight, nullptr, exclude,
+                                 threshold, max_out, out, n_out, s));
+}
+
+int aid_vibe_lane_filtered(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                           int32_t top_k_per_track, double diversity_weight, const aid_vec_filter *filters,
+                           const uint32_t *exclude, double threshold, int32_t max_out, aid_vibe_row *out,
+                           int32_t *n_out, void *stream) {
+    VEC_CALL(e, stream, vec_lane(e->vec, queries, nq, location, limit, top_k_per_track, diversity_weight, filters, exclude,
                                  threshold, max_out, out, n_out, s));
 }
 

@@ -18,6 +18,8 @@
 //
 // The opt-in int8 prefilter (FPSPEC 9.1, aid_vec_prefilter) answers the same searches from an int8 copy of the
 // catalog plus exact rescoring; its kernels are in csrc/vector_q8.hip, its host route (vec_search_q8) is here.
+// The opt-in filtered search (FPSPEC 9.2) narrows "live" to "passes this query's filter" on every route: K9f
+// (csrc/vector_filter.hip) writes a batch's allow-bitmaps, and the selection kernels read them through VecAllowed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -159,8 +161,10 @@ __global__ __launch_bounds__(256) void k_vec_scan_valu(const float *__restrict__
 
 // Slice blockIdx.x of query blockIdx.y: keys of `slice` inputs (scores of live entries on the first pass, the
 // previous pass's keys after it) sorted descending in LDS; the first `keep` go to out[q][slice_index][keep].
-__global__ __launch_bounds__(256) void k_vec_select(const float *__restrict__ scores, int64_t ns,
-                                                    const uint8_t *__restrict__ dead,
+// M (aidfp_vector_keys.h) says which entries count, here and in k_vec_slice_max and k_vec_filter: VecLive by
+// default, VecAllowed under a filter (FPSPEC 9.2).
+template <typename M>
+__global__ __launch_bounds__(256) void k_vec_select(const float *__restrict__ scores, int64_t ns, const M member,
                                                     const unsigned long long *__restrict__ in, int64_t in_stride,
                                                     int64_t n_in, int slice, int keep,
                                                     unsigned long long *__restrict__ out, int64_t out_stride) {
@@ -170,12 +174,13 @@ __global__ __launch_bounds__(256) void k_vec_select(const float *__restrict__ sc
     const int cnt = (int)min((int64_t)slice, n_in - base);
     int sp = 2;  // this slice's own padded size: a ragged last slice sorts less
     while (sp < cnt) sp <<= 1;
+    const auto mrow = member.row(q);
     for (int i = threadIdx.x; i < sp; i += 256) {
         unsigned long long key = 0;
         if (i < cnt) {
             if (scores) {
                 const int64_t e = base + i;
-                if (!dead[e]) key = vec_key(scores[(size_t)q * ns + e], (uint32_t)e);
+                if (M::test(mrow, e)) key = vec_key(scores[(size_t)q * ns + e], (uint32_t)e);
             } else {
                 key = in[(size_t)q * in_stride + base + i];
             }
@@ -194,16 +199,18 @@ __global__ __launch_bounds__(256) void k_vec_select(const float *__restrict__ sc
 // k_vec_filter appends the keys of the entries at or above it to the query's candidate list, which one
 // k_vec_select sorts. Candidates arrive in any order; their keys are distinct, so the sorted list is the same on
 // every run. A list that would overflow (many equal scores) sends the batch down the slice-by-slice route instead.
-__global__ __launch_bounds__(256) void k_vec_slice_max(const float *__restrict__ scores, int64_t ns,
-                                                       const uint8_t *__restrict__ dead, int64_t n, int slice, int n_slices,
+template <typename M>
+__global__ __launch_bounds__(256) void k_vec_slice_max(const float *__restrict__ scores, int64_t ns, const M member,
+                                                       int64_t n, int slice, int n_slices,
                                                        uint32_t *__restrict__ out) {
     __shared__ uint32_t part[4];
     const int q = blockIdx.y;
     const int64_t base = (int64_t)blockIdx.x * slice;
     const int64_t end = min(base + (int64_t)slice, n);
+    const auto mrow = member.row(q);
     uint32_t m = 0;
     for (int64_t e = base + threadIdx.x; e < end; e += 256)
-        if (!dead[e]) m = max(m, vec_score_key(scores[(size_t)q * ns + e]));
+        if (M::test(mrow, e)) m = max(m, vec_score_key(scores[(size_t)q * ns + e]));
     for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -223,16 +230,18 @@ __global__ __launch_bounds__(256) void k_vec_threshold(const uint32_t *__restric
     }
 }
 
-__global__ __launch_bounds__(256) void k_vec_filter(const float *__restrict__ scores, int64_t ns,
-                                                    const uint8_t *__restrict__ dead, int64_t n,
-                                                    const uint32_t *__restrict__ thr, unsigned long long *__restrict__ cand,
-                                                    int cap, int32_t *__restrict__ cnt) {
+template <typename M>
+__global__ __launch_bounds__(256) void k_vec_filter(const float *__restrict__ scores, int64_t ns, const M member,
+                                                    int64_t n, const uint32_t *__restrict__ thr,
+                                                    unsigned long long *__restrict__ cand, int cap,
+                                                    int32_t *__restrict__ cnt) {
     const int q = blockIdx.y;
     const uint32_t t = thr[q];
+    const auto mrow = member.row(q);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int64_t e = (int64_t)blockIdx.x * 2048 + j * 256 + threadIdx.x;
-        if (e < n && !dead[e]) {
+        if (e < n && M::test(mrow, e)) {
             const float s = scores[(size_t)q * ns + e];
             if (vec_score_key(s) >= t) {
                 const int pos = atomicAdd(&cnt[q], 1);
@@ -484,6 +493,8 @@ int vec_reset(VecCatalog &c, int dim) {
     c.h_chunk.clear();
     c.h_off.clear();
     c.h_dead.clear();
+    c.h_tags.clear();
+    c.tags_on_dev = 0;
     return AID_OK;
 }
 
@@ -521,7 +532,7 @@ static int vec_grow(VecCatalog &c, int64_t rows, hipStream_t s) {
 }
 
 int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index, const double *offset_sec,
-            int64_t n, int location, hipStream_t s) {
+            const uint64_t *tags, int64_t n, int location, hipStream_t s) {
     if (n < 0 || (location != AID_PCM_HOST && location != AID_PCM_DEVICE) || (n > 0 && (!vecs || !tracks || !offset_sec)))
         return vfail(c, AID_ERR_INVALID, "aid_vec_add: bad argument");
     if (!c.dim) return vfail(c, AID_ERR_STATE, "aid_vec_add: call aid_vec_reset first");
@@ -534,7 +545,9 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
     std::vector<uint32_t> tr(n);
     std::vector<int32_t> ch(n);
     std::vector<double> of(n);
+    std::vector<uint64_t> tg(n, 0);  // FPSPEC 9.2: 0 unless given
     if (location == AID_PCM_DEVICE) {
+        if (tags) VEC_TRY(hipMemcpyAsync(tg.data(), tags, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         VEC_TRY(hipMemcpyAsync(tr.data(), tracks, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         VEC_TRY(hipMemcpyAsync(of.data(), offset_sec, n * sizeof(double), hipMemcpyDeviceToHost, s));
         if (chunk_index) VEC_TRY(hipMemcpyAsync(ch.data(), chunk_index, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -543,6 +556,7 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
         memcpy(tr.data(), tracks, n * sizeof(uint32_t));
         memcpy(of.data(), offset_sec, n * sizeof(double));
         if (chunk_index) memcpy(ch.data(), chunk_index, n * sizeof(int32_t));
+        if (tags) memcpy(tg.data(), tags, n * sizeof(uint64_t));
     }
     if (!chunk_index)
         for (int64_t i = 0; i < n; ++i) ch[i] = (int32_t)i;
@@ -566,6 +580,7 @@ int vec_add(VecCatalog &c, const float *vecs, const uint32_t *tracks, const int3
     c.h_chunk.insert(c.h_chunk.end(), ch.begin(), ch.end());
     c.h_off.insert(c.h_off.end(), of.begin(), of.end());
     c.h_dead.insert(c.h_dead.end(), (size_t)n, (uint8_t)0);
+    c.h_tags.insert(c.h_tags.end(), tg.begin(), tg.end());  // the device column follows at the next filtered call
     c.n += n;
     c.n_live += n;
     return AID_OK;
@@ -582,6 +597,24 @@ int vec_remove(VecCatalog &c, uint32_t track, hipStream_t s) {
     c.n_live -= hit;
     VEC_TRY(hipMemcpyAsync(c.d_dead.p, c.h_dead.data(), c.n, hipMemcpyHostToDevice, s));
     VEC_TRY(hipStreamSynchronize(s));
+    return AID_OK;
+}
+
+int vec_retag(VecCatalog &c, uint32_t track, uint64_t tags) {
+    int64_t hit = 0;
+    for (int64_t i = 0; i < c.n; ++i)
+        if (c.h_track[i] == track && !c.h_dead[i]) {
+            c.h_tags[i] = tags;
+            ++hit;
+        }
+    if (!hit) return vfail(c, AID_ERR_INVALID, "aid_vec_retag: unknown or removed track");
+    c.tags_on_dev = 0;
+    return AID_OK;
+}
+
+int vec_tags(VecCatalog &c, uint64_t *out, int64_t cap) {
+    if (cap < c.n || (c.n > 0 && !out)) return vfail(c, AID_ERR_INVALID, "aid_vec_tags: out holds fewer than n_entries words");
+    if (c.n) memcpy(out, c.h_tags.data(), (size_t)c.n * sizeof(uint64_t));
     return AID_OK;
 }
 
@@ -639,7 +672,10 @@ int vec_compact(VecCatalog &c, int64_t *n_removed, hipStream_t s) {
         c.h_track[r] = c.h_track[map[r]];
         c.h_chunk[r] = c.h_chunk[map[r]];
         c.h_off[r] = c.h_off[map[r]];
+        c.h_tags[r] = c.h_tags[map[r]];
     }
+    c.h_tags.resize(m);
+    c.tags_on_dev = 0;
     c.h_track.resize(m);
     c.h_chunk.resize(m);
     c.h_off.resize(m);
@@ -741,9 +777,14 @@ static int vec_sel_plan(VecCatalog &c, int limit, VecSelPlan &p) {
     return AID_OK;
 }
 
-// The best p.limit keys of each of the batch's nb rows of d_scores, sorted, at (*in)[q * *in_stride ..].
-static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, hipStream_t s, unsigned long long **in_out,
-                            int64_t *in_stride_out) {
+static VecAllowed vec_allowed(const VecAllow &al) {
+    return VecAllowed{reinterpret_cast<const uint32_t *>(al.bm), al.fmap, al.words * 2};
+}
+
+// The best p.limit keys of each of the batch's nb rows of d_scores, sorted, at (*in)[q * *in_stride ..]. With
+// al.bm the entries that count are the ones the batch's allow-bitmaps pass (FPSPEC 9.2), not the live ones.
+static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, const VecAllow &al, hipStream_t s,
+                            unsigned long long **in_out, int64_t *in_stride_out) {
     const int64_t ns = (c.n + 31) / 32 * 32;
     const int limit = p.limit, slice = p.slice, keep = p.keep, mslice = p.mslice;
     const int64_t msl = p.msl;
@@ -752,21 +793,34 @@ static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, hipStrea
     if (p.by_threshold) {
         int32_t cnt[kVecQueryBatch];
         std::vector<int32_t> cnt_lines(p.q8 ? (size_t)nb * kVecQ8CntStride : 0);
-        hipLaunchKernelGGL(k_vec_slice_max, dim3((unsigned)msl, (unsigned)nb), dim3(256), 0, s, c.d_scores.p, ns,
-                           c.d_dead.p, c.n, mslice, (int)msl, c.d_smax.p);
+        if (al.bm)
+            hipLaunchKernelGGL(k_vec_slice_max<VecAllowed>, dim3((unsigned)msl, (unsigned)nb), dim3(256), 0, s, c.d_scores.p,
+                               ns, vec_allowed(al), c.n, mslice, (int)msl, c.d_smax.p);
+        else
+            hipLaunchKernelGGL(k_vec_slice_max<VecLive>, dim3((unsigned)msl, (unsigned)nb), dim3(256), 0, s, c.d_scores.p, ns,
+                               VecLive{c.d_dead.p}, c.n, mslice, (int)msl, c.d_smax.p);
         const int msp = std::max(2, pow2_ceil((int)msl));
         hipLaunchKernelGGL(k_vec_threshold, dim3((unsigned)nb), dim3(256), (size_t)msp * 4, s, c.d_smax.p, (int)msl, msp,
                            limit, c.d_thr.p, c.d_ccnt.p);
         VEC_TRY(hipMemsetAsync(c.d_cand.p, 0, (size_t)nb * kVecCandCap * 8, s));
         if (p.q8) {
             VEC_TRY(hipMemsetAsync(c.d_ccnt.p, 0, (size_t)nb * kVecQ8CntStride * sizeof(int32_t), s));
-            vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+            if (al.bm)
+                vec_q8_filter_allowed(c.d_scores.p, ns, al, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+            else
+                vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
             VEC_TRY(hipGetLastError());
             VEC_TRY(hipMemcpyAsync(cnt_lines.data(), c.d_ccnt.p, (size_t)nb * kVecQ8CntStride * sizeof(int32_t),
                                    hipMemcpyDeviceToHost, s));
         } else {
-            hipLaunchKernelGGL(k_vec_filter, dim3((unsigned)((c.n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s,
-                               c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p);
+            if (al.bm)
+                hipLaunchKernelGGL(k_vec_filter<VecAllowed>, dim3((unsigned)((c.n + 2047) / 2048), (unsigned)nb), dim3(256), 0,
+                                   s, c.d_scores.p, ns, vec_allowed(al), c.n, c.d_thr.p, c.d_cand.p, kVecCandCap,
+                                   c.d_ccnt.p);
+            else
+                hipLaunchKernelGGL(k_vec_filter<VecLive>, dim3((unsigned)((c.n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s,
+                                   c.d_scores.p, ns, VecLive{c.d_dead.p}, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap,
+                                   c.d_ccnt.p);
             VEC_TRY(hipGetLastError());
             VEC_TRY(hipMemcpyAsync(cnt, c.d_ccnt.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
@@ -778,9 +832,9 @@ static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, hipStrea
         ++c.st[most <= kVecCandCap ? 0 : 2];
         if (most <= kVecCandCap) {  // every list fits: one sort each
             const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
-            hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
-                               ns, c.d_dead.p, c.d_cand.p, (int64_t)kVecCandCap, (int64_t)one, one, keep, c.d_keys0.p,
-                               (int64_t)keep);
+            hipLaunchKernelGGL(k_vec_select<VecLive>, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s,
+                               (const float *)nullptr, ns, VecLive{c.d_dead.p}, c.d_cand.p, (int64_t)kVecCandCap,
+                               (int64_t)one, one, keep, c.d_keys0.p, (int64_t)keep);
             VEC_TRY(hipGetLastError());
             in = c.d_keys0.p;
             in_stride = keep;
@@ -794,9 +848,14 @@ static int vec_select_batch(VecCatalog &c, int nb, const VecSelPlan &p, hipStrea
         for (bool first = true;; first = false) {
             const int64_t nsl = (n_in + slice - 1) / slice;
             const int64_t out_stride = nsl * keep;
-            hipLaunchKernelGGL(k_vec_select, dim3((unsigned)nsl, (unsigned)nb), dim3(256), (size_t)pow2_ceil(slice) * 8, s,
-                               first ? c.d_scores.p : nullptr, ns, c.d_dead.p, in, in_stride, n_in, slice, keep, out,
-                               out_stride);
+            if (first && al.bm)  // only the first pass asks which entries count: the later ones sort its keys
+                hipLaunchKernelGGL(k_vec_select<VecAllowed>, dim3((unsigned)nsl, (unsigned)nb), dim3(256),
+                                   (size_t)pow2_ceil(slice) * 8, s, c.d_scores.p, ns, vec_allowed(al), in, in_stride, n_in,
+                                   slice, keep, out, out_stride);
+            else
+                hipLaunchKernelGGL(k_vec_select<VecLive>, dim3((unsigned)nsl, (unsigned)nb), dim3(256),
+                                   (size_t)pow2_ceil(slice) * 8, s, first ? c.d_scores.p : nullptr, ns, VecLive{c.d_dead.p}, in,
+                                   in_stride, n_in, slice, keep, out, out_stride);
             VEC_TRY(hipGetLastError());
             ++c.st[3];
             in = out;
@@ -823,12 +882,61 @@ static int vec_hits_batch(VecCatalog &c, const unsigned long long *in, int64_t i
 
 // FPSPEC 9 for one batch: the f32 scan, the selection, the hit columns.
 static int vec_f32_batch(VecCatalog &c, const float *dq, int nb, const VecSelPlan &p, int q0, const int32_t *qmap,
-                         hipStream_t s) {
+                         const VecAllow &al, hipStream_t s) {
     if (int rc = vec_scan_batch(c, dq, nb, s)) return rc;
     unsigned long long *in = nullptr;
     int64_t in_stride = 0;
-    if (int rc = vec_select_batch(c, nb, p, s, &in, &in_stride)) return rc;
+    if (int rc = vec_select_batch(c, nb, p, al, s, &in, &in_stride)) return rc;
     return vec_hits_batch(c, in, in_stride, p.keep, p.limit, nb, q0, qmap, s);
+}
+
+// ---- filtered search (FPSPEC 9.2). A call with filters plans all its batches first (c.h_fplans, empty for an
+// unfiltered call), brings the tags column up to date and reserves the scratch; each filtered batch then stages its
+// distinct filters and runs K9f before its selection.
+static int vec_filters_begin(VecCatalog &c, const aid_vec_filter *filters, int nq, hipStream_t s) {
+    c.h_fplans.clear();
+    if (!filters || c.n == 0) return AID_OK;
+    bool any = false;
+    for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
+        c.h_fplans.emplace_back();
+        vec_filter_plan(filters + q0, std::min(kVecQueryBatch, nq - q0), c.h_fplans.back());
+        any = any || c.h_fplans.back().filtered;
+    }
+    if (!any) {
+        c.h_fplans.clear();
+        return AID_OK;
+    }
+    if (c.d_tags.n < (size_t)c.n) {
+        VEC_TRY(c.d_tags.reserve((size_t)c.cap_rows));
+        c.tags_on_dev = 0;
+    }
+    if (c.tags_on_dev < c.n) {
+        VEC_TRY(hipMemcpyAsync(c.d_tags.p + c.tags_on_dev, c.h_tags.data() + c.tags_on_dev,
+                               (size_t)(c.n - c.tags_on_dev) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        VEC_TRY(hipStreamSynchronize(s));
+        c.tags_on_dev = c.n;
+    }
+    VEC_TRY(c.d_filters.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(c.d_fmap.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(c.d_fmap_fb.reserve((size_t)kVecQueryBatch));
+    VEC_TRY(c.d_allow.reserve((size_t)kVecQueryBatch * vec_allow_words(c.n)));
+    return AID_OK;
+}
+
+// The allow-bitmaps of batch b of the call; `al` stays empty for an unfiltered batch, which then takes FPSPEC 9's
+// kernels on their arguments.
+static int vec_allow_batch(VecCatalog &c, size_t b, hipStream_t s, VecAllow &al) {
+    al = VecAllow{};
+    if (b >= c.h_fplans.size() || !c.h_fplans[b].filtered) return AID_OK;
+    const VecFilterPlan &p = c.h_fplans[b];
+    VEC_TRY(hipMemcpyAsync(c.d_filters.p, p.distinct, (size_t)p.n_distinct * sizeof(aid_vec_filter), hipMemcpyHostToDevice, s));
+    VEC_TRY(hipMemcpyAsync(c.d_fmap.p, p.fmap, sizeof p.fmap, hipMemcpyHostToDevice, s));
+    vec_allow(c.d_dead.p, c.d_track.p, c.d_tags.p, c.n, c.d_filters.p, p.n_distinct, c.d_allow.p, s);
+    VEC_TRY(hipGetLastError());
+    al.bm = c.d_allow.p;
+    al.fmap = c.d_fmap.p;
+    al.words = vec_allow_words(c.n);
+    return AID_OK;
 }
 
 // Normalise queries [q0, q0 + nb) into c.d_q, quantise the tiles (FPSPEC 9.1) into d_q8 / d_qs / d_qe and score
@@ -868,14 +976,19 @@ static int vec_search_q8(VecCatalog &c, const float *dq, int nq, const VecSelPla
     for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
         const int nb = std::min(kVecQueryBatch, nq - q0);
         const float *dqb = dq + (size_t)q0 * dim;
+        VecAllow al;  // FPSPEC 9.2: "live" reads "passes" in the first stage, in W and in the fallback
+        if (int rc = vec_allow_batch(c, (size_t)(q0 / kVecQueryBatch), s, al)) return rc;
         if (int rc = vec_q8_scan_batch(c, dqb, nb, s)) return rc;
         unsigned long long *in = nullptr;
         int64_t in_stride = 0;
-        if (int rc = vec_select_batch(c, nb, pr, s, &in, &in_stride)) return rc;  // the R best by approx
+        if (int rc = vec_select_batch(c, nb, pr, al, s, &in, &in_stride)) return rc;  // the R best by approx
         VEC_TRY(vec_q8_rescore(c.d_vecs.p, c.d_q.p, dim, in, in_stride, R, nullptr, 0, nb, s));
         vec_q8_tau(in, in_stride, R, limit, c.d_qe.p, c.q8_E, dim, c.d_thr.p, c.d_ccnt.p, nb, s);
         VEC_TRY(hipMemsetAsync(c.d_cand.p, 0, (size_t)nb * kVecCandCap * 8, s));
-        vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+        if (al.bm)
+            vec_q8_filter_allowed(c.d_scores.p, ns, al, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
+        else
+            vec_q8_filter(c.d_scores.p, ns, c.d_dead.p, c.n, c.d_thr.p, c.d_cand.p, kVecCandCap, c.d_ccnt.p, nb, s);
         VEC_TRY(hipGetLastError());
         int32_t cnt[kVecQueryBatch], fb[kVecQueryBatch];
         std::vector<int32_t> cnt_lines((size_t)nb * kVecQ8CntStride);
@@ -899,9 +1012,9 @@ static int vec_search_q8(VecCatalog &c, const float *dq, int nq, const VecSelPla
         if (nfb < nb) {
             VEC_TRY(vec_q8_rescore(c.d_vecs.p, c.d_q.p, dim, c.d_cand.p, kVecCandCap, most, c.d_ccnt.p, wcap, nb, s));
             const int one = std::max(2 * pow2_ceil(limit), pow2_ceil(most));  // <= kVecCandCap
-            hipLaunchKernelGGL(k_vec_select, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s, (const float *)nullptr,
-                               ns, c.d_dead.p, c.d_cand.p, (int64_t)kVecCandCap, (int64_t)one, one, pl.keep, c.d_keys0.p,
-                               (int64_t)pl.keep);
+            hipLaunchKernelGGL(k_vec_select<VecLive>, dim3(1, (unsigned)nb), dim3(256), (size_t)one * 8, s,
+                               (const float *)nullptr, ns, VecLive{c.d_dead.p}, c.d_cand.p, (int64_t)kVecCandCap,
+                               (int64_t)one, one, pl.keep, c.d_keys0.p, (int64_t)pl.keep);
             VEC_TRY(hipGetLastError());
             // the columns of a query that fell back hold an unfinished list until the f32 route rewrites them below
             if (int rc = vec_hits_batch(c, c.d_keys0.p, pl.keep, pl.keep, limit, nb, q0, nullptr, s)) return rc;
@@ -913,15 +1026,23 @@ static int vec_search_q8(VecCatalog &c, const float *dq, int nq, const VecSelPla
                 VEC_TRY(hipMemcpyAsync(c.d_fbq.p + (size_t)j * dim, dqb + (size_t)fb[j] * dim, (size_t)dim * sizeof(float),
                                        hipMemcpyDeviceToDevice, s));
             VEC_TRY(hipMemcpyAsync(c.d_qmap.p, fb, (size_t)nfb * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            VecAllow al_fb = al;
+            if (al.bm) {  // query j of the tile is query fb[j] of the batch: it keeps that query's bitmap
+                const VecFilterPlan &fp = c.h_fplans[(size_t)(q0 / kVecQueryBatch)];
+                for (int j = 0; j < nfb; ++j) c.h_fmap_fb[j] = fp.fmap[fb[j]];
+                VEC_TRY(hipMemcpyAsync(c.d_fmap_fb.p, c.h_fmap_fb, (size_t)nfb * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                al_fb.fmap = c.d_fmap_fb.p;
+            }
             VEC_TRY(hipStreamSynchronize(s));
-            if (int rc = vec_f32_batch(c, c.d_fbq.p, nfb, pl, q0, c.d_qmap.p, s)) return rc;
+            if (int rc = vec_f32_batch(c, c.d_fbq.p, nfb, pl, q0, c.d_qmap.p, al_fb, s)) return rc;
         }
     }
     return AID_OK;
 }
 
 // Hit columns of all nq queries on the device: d_hentry / d_htrack / d_hscore / d_hoff [nq][limit], d_nhits [nq].
-static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int location, int limit, hipStream_t s) {
+static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int location, int limit,
+                          const aid_vec_filter *filters, hipStream_t s) {
     const size_t nh = (size_t)nq * limit;
     VEC_TRY(c.d_hentry.reserve(nh));
     VEC_TRY(c.d_htrack.reserve(nh));
@@ -934,21 +1055,33 @@ static int vec_search_dev(VecCatalog &c, const float *queries, int nq, int locat
     if (int rc = vec_stage_queries(c, queries, nq, location, s, &dq)) return rc;
     VecSelPlan pl;
     if (int rc = vec_sel_plan(c, limit, pl)) return rc;
+    if (int rc = vec_filters_begin(c, filters, nq, s)) return rc;
     if (c.q8_mode) return vec_search_q8(c, dq, nq, pl, s);
     for (int q0 = 0; q0 < nq; q0 += kVecQueryBatch) {
         const int nb = std::min(kVecQueryBatch, nq - q0);
-        if (int rc = vec_f32_batch(c, dq + (size_t)q0 * c.dim, nb, pl, q0, nullptr, s)) return rc;
+        VecAllow al;
+        if (int rc = vec_allow_batch(c, (size_t)(q0 / kVecQueryBatch), s, al)) return rc;
+        if (int rc = vec_f32_batch(c, dq + (size_t)q0 * c.dim, nb, pl, q0, nullptr, al, s)) return rc;
     }
     return AID_OK;
 }
 
-int vec_search(VecCatalog &c, const float *queries, int nq, int location, int limit, aid_vec_hit *hits, int32_t *n_hits,
-               hipStream_t s) {
+static int vec_filter_args(VecCatalog &c, const char *what, const aid_vec_filter *filters, int nq) {
+    if (filters && nq > 0)
+        if (const int bad = vec_filters_invalid(filters, nq))
+            return vfail(c, AID_ERR_INVALID, std::string(what) + ": filter " + std::to_string(bad - 1) +
+                                                 " excludes more than 8 tracks");
+    return AID_OK;
+}
+
+int vec_search(VecCatalog &c, const float *queries, int nq, int location, int limit, const aid_vec_filter *filters,
+               aid_vec_hit *hits, int32_t *n_hits, hipStream_t s) {
     if (int rc = vec_query_args(c, "aid_vec_search", queries, nq, location)) return rc;
     if (limit < 1 || limit > kVecMaxLimit || (nq > 0 && (!hits || !n_hits)))
         return vfail(c, AID_ERR_INVALID, "aid_vec_search: limit must be in [1, 1024] and hits, n_hits non-null");
+    if (int rc = vec_filter_args(c, "aid_vec_search_filtered", filters, nq)) return rc;
     if (nq == 0) return AID_OK;
-    if (int rc = vec_search_dev(c, queries, nq, location, limit, s)) return rc;
+    if (int rc = vec_search_dev(c, queries, nq, location, limit, filters, s)) return rc;
     const size_t nh = (size_t)nq * limit;
     std::vector<uint32_t> he(nh);
     std::vector<float> hs(nh);
@@ -1099,18 +1232,20 @@ int vec_aggregate(VecCatalog &c, const aid_vec_hit *hits, const int64_t *hoff, i
 }
 
 int vec_lane(VecCatalog &c, const float *queries, int nq, int location, int limit, int top_k, double weight,
-             const uint32_t *exclude, double threshold, int max_out, aid_vibe_row *out, int32_t *n_out, hipStream_t s) {
+             const aid_vec_filter *filters, const uint32_t *exclude, double threshold, int max_out, aid_vibe_row *out,
+             int32_t *n_out, hipStream_t s) {
     if (int rc = vec_query_args(c, "aid_vibe_lane", queries, nq, location)) return rc;
     if (limit < 1 || limit > kVecMaxLimit) return vfail(c, AID_ERR_INVALID, "aid_vibe_lane: limit must be in [1, 1024]");
     if (int rc = vec_agg_args(c, "aid_vibe_lane", top_k, max_out, nq, out, n_out)) return rc;
+    if (int rc = vec_filter_args(c, "aid_vibe_lane_filtered", filters, nq)) return rc;
     if (nq == 0) return AID_OK;
-    if (int rc = vec_search_dev(c, queries, nq, location, limit, s)) return rc;
+    if (int rc = vec_search_dev(c, queries, nq, location, limit, filters, s)) return rc;
     return vec_agg_run(c, c.d_htrack.p, c.d_hscore.p, c.d_hoff.p, nullptr, c.d_nhits.p, limit, nq, top_k, weight, exclude,
                        threshold, max_out, out, n_out, s);
 }
 
 // ---- persistence: magic, version, dim, n, then the tiles of ceil(n / 32) * 32 rows as stored, tracks, chunk
-// indices, offsets, tombstones
+// indices, offsets, tombstones, and in version 2 the tags (FPSPEC 9.2)
 namespace {
 struct VecFileHeader {
     char magic[8];
@@ -1134,7 +1269,10 @@ int vec_save(VecCatalog &c, const char *path, hipStream_t s) {
     if (!f) return vfail(c, AID_ERR_INVALID, std::string("aid_vec_save: cannot open ") + path);
     VecFileHeader h;
     memcpy(h.magic, kVecMagic, 8);
-    h.version = 1;
+    // version 2 = version 1 with the tags column (FPSPEC 9.2) after the tombstones; a catalog without a tag saves
+    // the file it always saved
+    const bool tagged = std::any_of(c.h_tags.begin(), c.h_tags.end(), [](uint64_t t) { return t != 0; });
+    h.version = tagged ? 2 : 1;
     h.dim = c.dim;
     h.n = c.n;
     const size_t n = (size_t)c.n;
@@ -1142,6 +1280,7 @@ int vec_save(VecCatalog &c, const char *path, hipStream_t s) {
     ok = ok && (!nf || fwrite(v.data(), sizeof(float), nf, f) == nf);
     ok = ok && (!n || (fwrite(c.h_track.data(), 4, n, f) == n && fwrite(c.h_chunk.data(), 4, n, f) == n &&
                        fwrite(c.h_off.data(), 8, n, f) == n && fwrite(c.h_dead.data(), 1, n, f) == n));
+    ok = ok && (!tagged || fwrite(c.h_tags.data(), 8, n, f) == n);
     ok = (fclose(f) == 0) && ok;
     if (!ok) return vfail(c, AID_ERR_INVALID, std::string("aid_vec_save: write failed: ") + path);
     return AID_OK;
@@ -1152,8 +1291,9 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
     FILE *f = fopen(path, "rb");
     if (!f) return vfail(c, AID_ERR_INVALID, std::string("aid_vec_load: cannot open ") + path);
     VecFileHeader h;
-    bool ok = fread(&h, sizeof h, 1, f) == 1 && memcmp(h.magic, kVecMagic, 8) == 0 && h.version == 1 &&
+    bool ok = fread(&h, sizeof h, 1, f) == 1 && memcmp(h.magic, kVecMagic, 8) == 0 && (h.version == 1 || h.version == 2) &&
               vec_dim_ok(h.dim) && h.n >= 0 && h.n < 0xFFFFFFFFll;
+    std::vector<uint64_t> tg;
     std::vector<float> v;
     std::vector<uint32_t> tr;
     std::vector<int32_t> ch;
@@ -1161,7 +1301,7 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
     std::vector<uint8_t> dead;
     if (ok) {
         const size_t n = (size_t)h.n, nf = (size_t)((h.n + 31) / 32) * 32 * h.dim;
-        const long want = (long)(sizeof h + nf * 4 + n * 17);
+        const long want = (long)(sizeof h + nf * 4 + n * (h.version == 2 ? 25 : 17));
         ok = fseek(f, 0, SEEK_END) == 0 && ftell(f) == want && fseek(f, (long)sizeof h, SEEK_SET) == 0;
         if (ok) {
             v.resize(nf);
@@ -1172,6 +1312,8 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
             ok = (!nf || fread(v.data(), 4, nf, f) == nf) &&
                  (!n || (fread(tr.data(), 4, n, f) == n && fread(ch.data(), 4, n, f) == n &&
                          fread(of.data(), 8, n, f) == n && fread(dead.data(), 1, n, f) == n));
+            tg.assign(n, 0);  // version 1: no entry is tagged
+            ok = ok && (h.version != 2 || !n || fread(tg.data(), 8, n, f) == n);
         }
     }
     fclose(f);
@@ -1195,6 +1337,7 @@ int vec_load(VecCatalog &c, const char *path, hipStream_t s) {
     c.h_chunk.swap(ch);
     c.h_off.swap(of);
     c.h_dead.swap(dead);
+    c.h_tags.swap(tg);
     if (c.q8_mode) return vec_q8_rebuild(c, s);  // the file holds no int8 form: it follows from the f32 rows
     return AID_OK;
 }

@@ -223,17 +223,19 @@ __global__ __launch_bounds__(256) void k_vec_rescore(const float *__restrict__ c
 // k_vec_filter for the prefilter's two candidate lists, which are longer than the f32 route's (R and |W| against
 // `limit`): the same test and the same keys, but query q counts in cnt[q * kVecQ8CntStride], a 128-byte line of its
 // own, so the appends of different queries do not queue behind one another in one L2 line.
-__global__ __launch_bounds__(256) void k_vec_filter_q8(const float *__restrict__ scores, int64_t ns,
-                                                       const uint8_t *__restrict__ dead, int64_t n,
-                                                       const uint32_t *__restrict__ thr,
+// M: which entries count, as in k_vec_filter (VecLive, or VecAllowed under a filter, FPSPEC 9.2).
+template <typename M>
+__global__ __launch_bounds__(256) void k_vec_filter_q8(const float *__restrict__ scores, int64_t ns, const M member,
+                                                       int64_t n, const uint32_t *__restrict__ thr,
                                                        unsigned long long *__restrict__ cand, int cap,
                                                        int32_t *__restrict__ cnt) {
     const int q = blockIdx.y;
     const uint32_t t = thr[q];
+    const auto mrow = member.row(q);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int64_t e = (int64_t)blockIdx.x * 2048 + j * 256 + threadIdx.x;
-        if (e < n && !dead[e]) {
+        if (e < n && M::test(mrow, e)) {
             const float s = scores[(size_t)q * ns + e];
             if (vec_score_key(s) >= t) {
                 const int pos = atomicAdd(&cnt[(size_t)q * kVecQ8CntStride], 1);
@@ -301,8 +303,15 @@ hipError_t vec_q8_rescore(const float *cat, const float *q, int dim, unsigned lo
 
 void vec_q8_filter(const float *scores, int64_t ns, const uint8_t *dead, int64_t n, const uint32_t *thr,
                    unsigned long long *cand, int cap, int32_t *cnt, int nb, hipStream_t s) {
-    hipLaunchKernelGGL(k_vec_filter_q8, dim3((unsigned)((n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s, scores, ns, dead, n,
-                       thr, cand, cap, cnt);
+    hipLaunchKernelGGL(k_vec_filter_q8<VecLive>, dim3((unsigned)((n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s, scores, ns,
+                       VecLive{dead}, n, thr, cand, cap, cnt);
+}
+
+void vec_q8_filter_allowed(const float *scores, int64_t ns, const VecAllow &al, int64_t n, const uint32_t *thr,
+                           unsigned long long *cand, int cap, int32_t *cnt, int nb, hipStream_t s) {
+    hipLaunchKernelGGL(k_vec_filter_q8<VecAllowed>, dim3((unsigned)((n + 2047) / 2048), (unsigned)nb), dim3(256), 0, s, scores,
+                       ns, VecAllowed{reinterpret_cast<const uint32_t *>(al.bm), al.fmap, al.words * 2}, n, thr, cand, cap,
+                       cnt);
 }
 
 void vec_q8_tau(const unsigned long long *keys, int64_t stride, int R, int limit, const float *q_e, float E, int dim,

@@ -419,7 +419,8 @@ int aid_vibe_lane(aid_engine *e, const float *queries, int32_t nq, int32_t locat
                   int32_t max_out, aid_vibe_row *out, int32_t *n_out, void *stream);
 /* Flat versioned file (magic AIDFPVC1, u32 version, i32 dim, i64 n, then the normalised vectors as stored, tracks,
    chunk indices, offsets, tombstones): replaces Qdrant's own persistence. A truncated or foreign file gives
-   AID_ERR_INVALID and leaves the catalog as it was. */
+   AID_ERR_INVALID and leaves the catalog as it was. A catalog with a non-zero tags word (FPSPEC 9.2) saves version
+   2, the same file with the u64 tags column appended; one without saves version 1 as before. Load reads both. */
 int aid_vec_save(aid_engine *e, const char *path);
 int aid_vec_load(aid_engine *e, const char *path);
 /* Cumulative vector-lane counters since the last reset (the first n of 8), counted on the host. A batch is one scan +
@@ -447,6 +448,40 @@ int aid_vec_scores_i8(aid_engine *e, const float *queries, int32_t nq, int32_t l
    rescored with the FPSPEC 9 chain (first-stage candidates and the W of the answered queries), [5] int8 scan
    launches (aid_vec_scores_i8 counts here as well). The selection over approx also counts in aid_vec_stats. */
 int aid_vec_prefilter_stats(aid_engine *e, int64_t *out, int32_t n, int32_t reset);
+/* Filtered search (spec/FPSPEC.md 9.2; K9f, csrc/vector_filter.hip), opt-in: the calls above do what they did.
+   Every entry carries a 64-bit `tags` word, 0 unless given here. A filter belongs to one query; entry e passes it
+   iff e is live, (any_of == 0 or tags_e & any_of != 0), tags_e & all_of == all_of, tags_e & none_of == 0, and
+   track_e is not among the first n_exclude ids of `exclude` (an id that no entry carries is not an error). The hit
+   list of a filtered query is FPSPEC 9's with "live" read as "passes": the filter acts before the selection, so
+   an excluded track takes no slot. The all-zero filter passes exactly the live entries. */
+#define AID_VEC_MAX_EXCLUDE 8
+typedef struct aid_vec_filter {
+    uint64_t any_of, all_of, none_of;
+    uint32_t n_exclude;
+    uint32_t exclude[AID_VEC_MAX_EXCLUDE];
+} aid_vec_filter;
+/* aid_vec_add with a tags column [n] (NULL = all 0; host or device, as the other payload columns). aid_vec_add is
+   this call with NULL. */
+int aid_vec_add_tagged(aid_engine *e, const float *vecs, const uint32_t *tracks, const int32_t *chunk_index,
+                       const double *offset_sec, const uint64_t *tags, int64_t n, int32_t location);
+/* Set the tags word of every live entry of a track; AID_ERR_INVALID if it has no live entry. */
+int aid_vec_retag(aid_engine *e, uint32_t track, uint64_t tags);
+/* The tags column [n_entries] to host `out` (capacity `cap` words). */
+int aid_vec_tags(aid_engine *e, uint64_t *out, int64_t cap);
+/* aid_vec_search under per-query filters: `filters` is host [nq], or NULL, which is aid_vec_search itself. A query
+   with fewer than `limit` passing entries gets a shorter list, with none n_hits = 0. n_exclude > 8 gives
+   AID_ERR_INVALID before anything runs. A batch of 64 queries whose filters are all zero runs the unfiltered
+   kernels. Filtered batches count in aid_vec_stats and aid_vec_prefilter_stats as the others do; the prefilter's
+   rescored pairs ([4]) are counted on the host from the live count, so a filtered query adds min(R, n_live) for its
+   first stage even where fewer entries pass. */
+int aid_vec_search_filtered(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                            const aid_vec_filter *filters, aid_vec_hit *hits, int32_t *n_hits, void *stream);
+/* aid_vibe_lane under per-query filters (host [nq], or NULL), in one critical section. `exclude` keeps its meaning
+   (dropped in the aggregation, after the track has taken its hit slots) and may be combined with a filter. */
+int aid_vibe_lane_filtered(aid_engine *e, const float *queries, int32_t nq, int32_t location, int32_t limit,
+                           int32_t top_k_per_track, double diversity_weight, const aid_vec_filter *filters,
+                           const uint32_t *exclude, double threshold, int32_t max_out, aid_vibe_row *out,
+                           int32_t *n_out, void *stream);
 
 /* ---- CLAP log-mel front end (spec/FPSPEC.md 10; K10, csrc/mel.hip) ----
  * What the reference computes on the host before its CLAP model sees a sample: chunk_audio (10 s chunks, 5 s hop,
