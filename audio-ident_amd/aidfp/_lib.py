@@ -25,6 +25,7 @@ AID_SYNTH_ASYNC = 2
 (AID_FORCE_K5_PATH, AID_FORCE_K5_PARTS, AID_FORCE_K5_BATCH, AID_FORCE_K2_STRIPS_X100, AID_FORCE_K4_BUILD,
  AID_FORCE_EXCHANGE_FAIL, AID_FORCE_LANE_GATHER, AID_FORCE_PLANE_ROWS, AID_FORCE_K2_WIDTH) = 1, 2, 3, 4, 5, 6, 7, 8, 9
 AID_FORCE_VEC_PATH, AID_FORCE_VEC_CHUNK, AID_FORCE_SPEED_GROUP, AID_FORCE_ROWS_MERGE = 10, 11, 12, 13
+AID_FORCE_K1_WAVES = 15
 AID_FORCE_VEC_CAND = 14
 AID_K_STFT, AID_K_PEAKS, AID_K_LANDMARK_COUNT, AID_K_LANDMARK_WRITE, AID_K_SYNTH, AID_K_MATCH = range(6)
 AID_K_RESAMPLE_SPEEDS, AID_K_SPEED_SELECT, AID_K_ROWS_MERGE, AID_K_INDEX_MERGE = 12, 13, 14, 15

@@ -303,7 +303,8 @@ class Engine:
              "exchange_fail": L.AID_FORCE_EXCHANGE_FAIL, "lane_gather": L.AID_FORCE_LANE_GATHER,
              "plane_rows": L.AID_FORCE_PLANE_ROWS, "k2_width": L.AID_FORCE_K2_WIDTH,
              "vec_path": L.AID_FORCE_VEC_PATH, "vec_chunk": L.AID_FORCE_VEC_CHUNK, "vec_cand": L.AID_FORCE_VEC_CAND,
-             "speed_group": L.AID_FORCE_SPEED_GROUP, "rows_merge": L.AID_FORCE_ROWS_MERGE}
+             "speed_group": L.AID_FORCE_SPEED_GROUP, "rows_merge": L.AID_FORCE_ROWS_MERGE,
+             "k1_waves": L.AID_FORCE_K1_WAVES}
 
     def force(self, what: str, value: int) -> None:
         """Test hook (aid_engine_force): pin one of the engine's own code paths, e.g. force("k5_path", 2)."""

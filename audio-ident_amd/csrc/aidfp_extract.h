@@ -29,6 +29,7 @@ struct Extractor {
     K2Policy k2;
     int64_t k2_slots[2] = {1, 1};  // resident K2 workgroups on the device (CUs x blocks per CU) at width 2, 4
     int64_t k1_slots = 1;          // resident K1 waves (CUs x kStftWaves: one K1 workgroup per CU)
+    int64_t k1_waves = 0;          // aid_engine_force K1_WAVES: the wave count K1 splits over (0 = k1_slots)
     int64_t plane_rows = 0;        // aid_engine_force PLANE_ROWS: power rows per clip group (0 = kPlaneRows)
     ExtractPlan plan;  // of the last call: what the result readers, the queries and the index append go by
     bool have_result = false;  // false while a call that failed leaves the plan and the buffers out of step

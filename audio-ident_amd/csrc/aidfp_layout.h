@@ -51,8 +51,8 @@ inline int peak_strip_len(const int64_t *frames, int n, int64_t slots) {
 
 // K1 -> K2 hot word of a power row (u64): bit hot_bit(c) is set when some bin of the 16-bin chunk c
 // (bins 16c .. 16c+15) is > thr. Chunks below 32 map to bit c, the others to bit 95 - c: the order in
-// which K1's lanes hold the mirror bins 1024 - k (stft.hip), so K1 builds the word with two s_quadmask
-// per register and no bit shuffling.
+// which K1's lanes hold the mirror bins 1024 - k (stft.hip), so K1 builds the word from quad masks of its
+// ballots with no bit shuffling (aidfp_hotword.h).
 constexpr int hot_bit(int c) { return c < 32 ? c : 95 - c; }
 
 // K4/K5 CSR bucket of a landmark hash (FPSPEC 6: k1 = h >> 22, k2 = (h >> 12) & 1023, dt = h & 63, the 26 bits a

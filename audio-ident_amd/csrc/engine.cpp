@@ -22,6 +22,15 @@ extern "C" int aid_diag_k2_stamps(unsigned long long *out, int reset) {  // diag
 }
 #endif
 
+#if defined(AID_K1_STAMPS)
+namespace aid {
+int k1_stamps_read(unsigned long long *out, int waves);
+}
+extern "C" int aid_diag_k1_stamps(unsigned long long *out, int waves) {  // diagnostic build only
+    return aid::k1_stamps_read(out, waves);
+}
+#endif
+
 static thread_local std::string g_err;
 
 int fail(int code, const std::string &msg) {
@@ -213,6 +222,10 @@ int aid_engine_force(aid_engine *e, int32_t what, int32_t value) {
         case AID_FORCE_SPEED_GROUP:
             if (value < 0) return fail(AID_ERR_INVALID, "SPEED_GROUP must be >= 0");
             e->speed_group = value;
+            return AID_OK;
+        case AID_FORCE_K1_WAVES:
+            if (value < 0) return fail(AID_ERR_INVALID, "K1_WAVES must be >= 0");
+            e->ext.k1_waves = value;
             return AID_OK;
         case AID_FORCE_ROWS_MERGE:
             if (value != 0 && value != 1) return fail(AID_ERR_INVALID, "ROWS_MERGE: 0 or 1");

@@ -79,8 +79,8 @@ int extract_locked(aid_engine *e, const void *pcm, PcmFmt fmt, const int64_t *of
             {
                 ProfScope ps(e, AID_K_STFT, s, true);
                 launch_stft_power(dpcm, fmt == kS16, x.desc.p + g.first, g.n, g.frame0, g.frames, g.k1_strips,
-                                  x.k1_slots, e->cfg.hop, e->d_tab.p, x.power.p, false, x.hotw.p,
-                                  e->cfg.peak_threshold, keep_power, qmax, s);
+                                  x.k1_waves > 0 ? x.k1_waves : x.k1_slots, e->cfg.hop, e->d_tab.p, x.power.p, false,
+                                  x.hotw.p, e->cfg.peak_threshold, keep_power, qmax, s);
             }
             if (loc == AID_PCM_HOST && &g == &p.groups.back()) {
                 HIP_TRY(x.stage_ev.record(s));

@@ -25,6 +25,7 @@
 // The variants measured against this layout live in the git history
 // (commit c236449, the AID_K1_* switches).
 #include "aidfp_device.h"
+#include "aidfp_hotword.h"
 #include "aidfp_launch.h"
 
 #include <type_traits>
@@ -65,15 +66,40 @@ static_assert(e1_region(15, 1) + 64 <= 2 * aid::kStftLdsPerWave, "E1 regions exc
 
 namespace aid {
 
-// 16-lane groups of a wave-wide mask -> 4 bits: bit g = some lane of lanes 16g .. 16g+15 is set (two
-// s_quadmask_b64: 64 lanes -> 16 quads -> 4 groups of 4 quads). s_quadmask writes SCC: without the clobber hipcc
-// may compute a branch condition into SCC before these and branch on it after them
-__device__ __forceinline__ uint64_t group16(uint64_t m) {
-    uint64_t q, r;
-    asm("s_quadmask_b64 %0, %1" : "=s"(q) : "s"(m) : "scc");
-    asm("s_quadmask_b64 %0, %1" : "=s"(r) : "s"(q) : "scc");
-    return r;
+#if defined(AID_K1_STAMPS)
+// Diagnostic build only (build_ext.build(variant="k1stamps", defines=("AID_K1_STAMPS",)), probes/k1_stamps_probe.py):
+// what the ends of K1 cost. Wave g < kK1StampWaves leaves 6 words: s_memtime at entry, when the ring of its first
+// segment has landed (the first frame's window multiply is next) and at exit; s_memrealtime (100 MHz, one clock for
+// the whole device) at entry and at exit; its segment count (more than one: its range crossed a clip edge). The buffer
+// is the stamps' own: nothing else reads it.
+constexpr int kK1StampWaves = 8192, kK1StampWords = 6;
+__device__ unsigned long long g_k1_stamps[kK1StampWaves * kK1StampWords];
+int k1_stamps_read(unsigned long long *out, int waves) {
+    if (waves < 0 || waves > kK1StampWaves) return -1;
+    const size_t bytes = sizeof(unsigned long long) * kK1StampWords * (size_t)waves;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k1_stamps), bytes) == hipSuccess ? 0 : -2;
 }
+#endif
+
+// The two scalar instructions of the hot word's reduction (aidfp_hotword.h). s_quadmask writes SCC: without the
+// clobber hipcc may compute a branch condition into SCC before it and branch on it after it
+struct HotOpsGcn {
+    static __device__ __forceinline__ uint64_t quadmask(uint64_t m) {
+        uint64_t q;
+        asm("s_quadmask_b64 %0, %1" : "=s"(q) : "s"(m) : "scc");
+        return q;
+    }
+    static __device__ __forceinline__ uint32_t pack16(uint32_t lo, uint32_t hi) {
+        uint32_t r;
+        asm("s_pack_ll_b32_b16 %0, %1, %2" : "=s"(r) : "s"(lo), "s"(hi));
+        return r;
+    }
+    static __device__ __forceinline__ uint64_t pair(uint32_t lo, uint32_t hi) {
+        uint64_t r = (uint64_t)lo | (uint64_t)hi << 32;
+        asm("" : "+s"(r));
+        return r;
+    }
+};
 
 // power-row store, non-temporal (streaming): K1 0.268 -> 0.266 ms, K2 0.134 -> 0.130 ms same-box (r02)
 __device__ __forceinline__ void pstore(float *p, float v) {
@@ -143,6 +169,10 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                                                                 const Tables *__restrict__ tab, float *__restrict__ out,
                                                                 uint64_t *__restrict__ hot, float thr, int keep,
                                                                 uint32_t *__restrict__ qmax) {
+#if defined(AID_K1_STAMPS)
+    const unsigned long long st_in = __builtin_amdgcn_s_memtime(), st_rin = __builtin_amdgcn_s_memrealtime();
+    unsigned long long st_first = 0, st_segs = 0;
+#endif
     constexpr int PERIOD = 16 / ROWS;  // frames per full ring rotation
     constexpr int HOP2 = 64 * ROWS;    // hop in sample pairs
     typedef PcmRing<T> Ring;
@@ -178,6 +208,9 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     const float s1 = mq < 2 ? 1.0f : -1.0f;                     // butterfly over lanes (mq, mq ^ 2)
     const float s2 = (mq == 1 || mq == 2) ? -1.0f : 1.0f;       // butterfly over lanes (mq, mq ^ 1)
     const float s0 = lane == 0 ? 1.0f : -1.0f;  // sign of Z[0]'s mirror slot for i = 0 (Z[0] itself)
+    // mirror store 0 (bins 1024 - lane): lane 0 has no mirror bin (the dropped Nyquist bin) and stores bin 512
+    // there instead, so the store needs no exec-masked block
+    const int moff0 = lane == 0 ? 512 : 1024 - lane;
 
     for (int i = threadIdx.x; i < 512; i += kStftWaves * 64) {
         const int h = i >> 6, l = i & 63, a = 2 * h, b = 2 * h + 1;
@@ -225,6 +258,8 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     // maximum starts at +0 and is never NaN, and v_max_f32 returns its non-NaN operand: a NaN never raises it, +inf
     // does (the same rule as K2's pkey). asm, because hipcc puts a canonicalising v_max x, x, x before each fmaxf
     float qrun = 0.f;
+    uint32_t keepm = __builtin_amdgcn_readfirstlane(keep ? ~0u : 0u);  // keep mode stores every block
+    asm("" : "+s"(keepm));             // one OR per frame (hipcc turned it back into a select on `keep` at every use)
     typename Ring::slot ring[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) ring[r] = Ring::ld(src[64 * r]);
@@ -234,6 +269,9 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     // (an empty asm reading every ring register: hipcc must complete the loads before it)
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ring::pin(ring[r]);
+#if defined(AID_K1_STAMPS)
+    if (st_segs++ == 0) st_first = __builtin_amdgcn_s_memtime();
+#endif
 
     for (int f0 = 0; f0 < nfr; f0 += PERIOD) {
 #pragma unroll
@@ -371,8 +409,19 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                     // straight-line real split: all 16 powers first, then the row's hot word, then the
                     // stores of the hot blocks (scalar branches after the arithmetic, so no branch splits it)
                     // the row's hot word (aidfp_layout.h hot_bit): bit of 16-bin chunk c = some bin of c is > thr
-                    uint64_t hotw = 0;
+                    // aidfp_hotword.h: level-1 words of the last register, pairs of them, the mirror ballots' low dwords
+                    uint32_t qd[8], qm[8], pd[4], pq[4], m0[9];
                     float po[8], pm[8];
+                    // bin 512 pairs with itself: every lane computes it (same address, same value), so its store
+                    // and its hot bit need no lane-0 branch
+                    float p512;
+                    {
+                        const float2 a = buf[2];  // Z[512] (E3 slot 2)
+                        const float er = a.x + a.x, ei = a.y - a.y, orr = a.y + a.y, oi = a.x - a.x;
+                        const float2 tw = cmul(make_float2(orr, oi), t512);
+                        const float xr = er + tw.x, xi = ei + tw.y;
+                        p512 = __builtin_fmaf(xr, xr, xi * xi);
+                    }
                     float4 qa, qb, t2p;  // the b128 reads that serve bins i and i + 4
 #pragma unroll
                     for (int ii = 0; ii < 8; ++ii) {
@@ -403,35 +452,31 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                         // its re is fma(orr, -c, oi*s) = -fma(orr, c, -(oi*s)) (round-to-nearest is odd-symmetric)
                         // and its im is fma(orr, s, (-oi)*(-c)) = tw.y; so xr2 = er + (-tw.x), xi2 = -ei + tw.y
                         const float xr2 = er - tw.x, xi2 = tw.y - ei;
-                        // k = 0 (lane 0, i = 0): the mirror is the dropped Nyquist bin
-                        pm[i] = (i == 0 && lane == 0) ? 0.f : __builtin_fmaf(xr2, xr2, xi2 * xi2);
+                        // k = 0 (lane 0, i = 0): the mirror is the dropped Nyquist bin; the lane carries bin 512
+                        // instead (mirror store 0 writes it there; its ballot bit is never read)
+                        pm[i] = (i == 0 && lane == 0) ? p512 : __builtin_fmaf(xr2, xr2, xi2 * xi2);
                         // direct bins 64i + l: lanes 16g..16g+15 = chunk 4i + g -> bit 4i + g
-                        hotw |= group16(__ballot(po[i] > thr)) << (4 * i);
+                        qd[i] = hot_quads<HotOpsGcn>(__ballot(po[i] > thr));
                         // mirror bins 1024 - 64i - l: lanes 16g+1 .. 16g+16 = chunk 63 - 4i - g -> bit 32 + 4i + g;
-                        // lane 0 (bin 1024 - 64i, chunk 64 - 4i) -> bit 31 + 4i (lane 0 of register 0 is the
-                        // dropped Nyquist bin, never hot)
+                        // lane 0 (bin 1024 - 64i, chunk 64 - 4i) -> bit 31 + 4i (lane 0 of register 0 is never read)
                         const uint64_t hm = __ballot(pm[i] > thr);
-                        hotw |= group16(hm >> 1) << (32 + 4 * i);
-                        if (i > 0) hotw |= (hm & 1ull) << (31 + 4 * i);
+                        qm[i] = hot_quads_mirror<HotOpsGcn>(hm);
+                        m0[i] = (uint32_t)hm;
+                        if (i & 1) {  // register i - 1 came earlier in this order
+                            pd[i >> 1] = hot_pair<HotOpsGcn>(qd[i - 1], qd[i]);
+                            pq[i >> 1] = hot_pair<HotOpsGcn>(qm[i - 1], qm[i]);
+                        }
                     }
+                    m0[8] = (uint32_t)__ballot(p512 > thr);  // chunk 32
+                    const uint64_t hotw = hot_word<HotOpsGcn>(pd, pq, m0);
                     // Wait here for the next frame's ring loads (issued after the window multiply, a frame's work
                     // ago: they have landed) and for the previous frame's stores. vmcnt counts loads and stores in
                     // issue order, and this frame's stores are conditional: without this wait hipcc waits at the next
                     // frame's window multiply with a count that only covers the unconditional stores, which also
                     // waits for the L2 acknowledgement of the hot stores issued just before
                     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-                    {  // bin 512 pairs with itself: every lane computes it (same address, same value),
-                       // so its store and the hot word's need no lane-0 branch
-                        const float2 a = buf[2];  // Z[512] (E3 slot 2)
-                        const float er = a.x + a.x, ei = a.y - a.y, orr = a.y + a.y, oi = a.x - a.x;
-                        const float2 tw = cmul(make_float2(orr, oi), t512);
-                        const float xr = er + tw.x, xi = ei + tw.y;
-                        const float p512 = __builtin_fmaf(xr, xr, xi * xi);
-                        pstore(drow + 512, p512);
-                        hotw |= p512 > thr ? 1ull << 63 : 0ull;  // chunk 32
-                        if constexpr (QMAX) asm("v_max_f32 %0, %0, %1" : "+v"(qrun) : "v"(p512));
-                    }
-                    if constexpr (QMAX) {  // the 16 registers the wave already holds (lane 0's pm[0] is 0)
+                    pstore(drow + 512, p512);
+                    if constexpr (QMAX) {  // the 16 registers the wave already holds (lane 0's pm[0] is bin 512)
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
                             asm("v_max_f32 %0, %0, %1" : "+v"(qrun) : "v"(po[i]));
@@ -443,15 +488,17 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
                     // 5), so a store whose chunks are all cold is skipped unless the engine keeps the whole
                     // plane. Direct store i covers chunks 4i .. 4i+3 (bits 4i..4i+3); mirror store i covers
                     // chunks 60-4i .. 63-4i (bits 32+4i .. 35+4i) and, by lane 0, chunk 64-4i (bit 31+4i)
-                    const uint64_t hsel = keep ? ~0ull : hotw;  // one select, not a branch per store
+                    // one bit per store (hot_stores), so a guard is a bit test and a branch (a nibble test of the
+                    // 64-bit word was and + mov + 64-bit compare + branch). __builtin_expect keeps the stores on
+                    // the fall-through path: without it hipcc put each behind a taken branch and a branch back
+                    const uint32_t hsel = hot_stores<HotOpsGcn>(hotw) | keepm;
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
-                        if ((hsel >> (4 * i)) & 0xFull) pstore(drow + lane + 64 * i, po[i]);
+                        if (__builtin_expect(hsel & (2u << i), 1)) pstore(drow + lane + 64 * i, po[i]);
+                    if (__builtin_expect(hsel & 0x200u, 1)) pstore(drow + moff0, pm[0]);  // lane 0: bin 512 again (same value)
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const uint64_t need = i > 0 ? (hsel >> (31 + 4 * i)) & 0x1Full : (hsel >> 32) & 0xFull;
-                        if (need && (i > 0 || lane != 0)) pstore(drow + 1024 - (lane + 64 * i), pm[i]);
-                    }
+                    for (int i = 1; i < 8; ++i)
+                        if (__builtin_expect(hsel & (0x200u << i), 1)) pstore(drow + 1024 - (lane + 64 * i), pm[i]);
                 } else {
                     // log-magnitude rows (aid_spectrogram: the 1e-4 check against float64 numpy), every bin.
                     // Real split in mirror pairs (k, 1024-k): one read of Z[k], Z[1024-k] serves both. For
@@ -510,6 +557,13 @@ __global__ __launch_bounds__(kStftWaves * 64) __attribute__((amdgpu_waves_per_eu
     }
     f += nfr;
     }
+#if defined(AID_K1_STAMPS)
+    if (g < kK1StampWaves && lane == 0) {
+        unsigned long long *st = g_k1_stamps + g * kK1StampWords;
+        st[0] = st_in, st[1] = st_first, st[2] = __builtin_amdgcn_s_memtime();
+        st[3] = st_rin, st[4] = __builtin_amdgcn_s_memrealtime(), st[5] = st_segs;
+    }
+#endif
 }
 
 template <bool LOGMAG, bool QMAX, typename T>

@@ -128,6 +128,8 @@ int aid_engine_config(const aid_engine *e, aid_config *out);
                                       does) and copy the merged rows out (tests: constructed lists through the kernel) */
 #define AID_FORCE_VEC_CAND 14      /* int8 prefilter: 0 default (4096), else the cap on |W| in [1, 4096] above which a
                                       query falls back to the f32 scan (tests: fallbacks on a small catalog) */
+#define AID_FORCE_K1_WAVES 15      /* 0 default (CUs x 16, the resident K1 waves), else the wave count K1 splits a call's
+                                      frames over (tests: small calls whose waves cross clip edges, or get few frames) */
 int aid_engine_force(aid_engine *e, int32_t what, int32_t value);
 
 /* Frames and worst-case record count of a clip of n samples (FPSPEC 1, 5). */
